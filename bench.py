@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- PriOr-RAFT inference throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one PriOr_RAFT forward (iters=12, test_mode=True) over one resident batch of
 synthetic 512x1024 ERP pairs per GPU (BASELINE.json configs[1]: one pair).  Ranks are
 independent (the path shards over image pairs; no data-path collective) => weak scaling;
-`value` = pairs processed by all ranks / max-over-ranks wall time of the K timed steps.
+`value` = pairs processed by all ranks / max-over-ranks wall time of the K timed steps,
+`ms_per_step` = that wall time / K.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--dump-outputs DIR` then also writes
+rank 0's flow of the last timed step (what the caller of the forward receives) as DIR/flow.npy, float32, at most 64 MB
+(a larger batch keeps a fixed, seeded sample of its pairs); weights and inputs are seeded, so two builds can be compared
+output for output.  `--full` adds the extra objects below (the --no-* options leave out parts of them).
 
 Multi-GPU: one process per GPU over torch.distributed ("nccl" = RCCL).  Either the caller provides the
 ranks (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`: RANK / LOCAL_RANK /
@@ -14,7 +20,7 @@ WORLD_SIZE / MASTER_* come from the environment), or `python bench.py --gpus N` 
 the parent makes NO GPU call, starts N fresh child processes of this script with that environment on
 127.0.0.1, relays rank 0's JSON line and exits with the worst child status.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only):
   roofline      the kernel with the largest summed time of one forward, WHATEVER its kind (every library launch is timed
                 with HIP events in a single-stream eager pass): an MFMA conv -> algorithmic FLOPs / time vs the dense bf16
                 MFMA peak (bf16x3 mode issues 3 MFMA FLOPs per algorithmic FLOP: mfma_pipe_util) or the fp32 MFMA peak;
@@ -96,13 +102,37 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1, help="pairs per GPU per step (configs[1] = 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: per-kernel rooflines, CPU baseline + parity, fp32, batch-32 and training-step legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's flow of the last timed step to DIR/flow.npy (float32, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the legs after it")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-batch32", action="store_true", help="skip the bounded configs[2] leg of the N=1 line")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the bounded training-step leg (configs[3] per GPU) of the N=1 line")
+    ap.add_argument("--no-batch32", action="store_true", help="with --full: skip the bounded configs[2] leg of the N=1 line")
+    ap.add_argument("--no-train-step", action="store_true",
+                    help="with --full: skip the bounded training-step leg (configs[3] per GPU) of the N=1 line")
     ap.add_argument("--precision", choices=["bf16x3", "fp32"], default=None,
                     help="update-block conv arithmetic (default: PRIORFLOW_PRECISION or bf16x3)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, flow):
+    """--dump-outputs: the flow [B, 2, H, W] of the last timed step as float32 .npy.  A batch larger than DUMP_LIMIT_BYTES keeps a
+    seeded sample of whole pairs (the same pairs, in batch order, on every run with the same arguments)."""
+    import numpy as np
+    a = flow.detach().float().cpu().contiguous()
+    keep = max(1, DUMP_LIMIT_BYTES // (a[:1].numel() * 4))
+    if a.shape[0] > keep:
+        a = a[torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "flow.npy"), a.numpy())
+    log(f"wrote {os.path.join(out_dir, 'flow.npy')}: {tuple(a.shape)} float32")
 
 
 def build_model(device):
@@ -658,7 +688,6 @@ def main():
     if world > 1:
         dist, backend = init_ranks(world, rank, device)
 
-    select_profile(args.batch, world)
     log(f"rank {rank}/{world} on {torch.cuda.get_device_name(local)}; building model")
     model, params = build_model(device)
     if args.precision is not None:
@@ -702,6 +731,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         world = dist.get_world_size()                        # the size the communicator really has
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, flow)
 
     result = None
     if rank == 0:
@@ -727,37 +758,39 @@ def main():
                        "hip_graph": bool(model.use_graph),
                        "encoders": "libpriorflow_hip.so (HIP kernels, both precisions)"},
         }
-        try:
-            log("per-kernel HIP-event pass")
-            result.update(profile_kernels(model, i1, i2))
-        except Exception as exc:  # measured extras must not hide the headline number
-            result["roofline"] = {"error": repr(exc)}
-        if world == 1 and not args.no_cpu_baseline:
-            ref_cpu = None
+        if args.full:
+            select_profile(args.batch, world)
             try:
-                # bounded sample: the first pair of the batch (a pair's result does not depend on its batch mates)
-                result["cpu_baseline"], result["parity"], ref_cpu = cpu_baseline(params, i1c[:1], i2c[:1], flow[:1])
-            except Exception as exc:
-                result["cpu_baseline"] = {"error": repr(exc)}
-            if model._weights()["precision"] == 1:
+                log("per-kernel HIP-event pass")
+                result.update(profile_kernels(model, i1, i2))
+            except Exception as exc:  # measured extras must not hide the headline number
+                result["roofline"] = {"error": repr(exc)}
+            if world == 1 and not args.no_cpu_baseline:
+                ref_cpu = None
                 try:
-                    result["fp32_exact"] = fp32_reference_point(params, device, i1[:1], i2[:1], ref_cpu)
+                    # bounded sample: the first pair of the batch (a pair's result does not depend on its batch mates)
+                    result["cpu_baseline"], result["parity"], ref_cpu = cpu_baseline(params, i1c[:1], i2c[:1], flow[:1])
                 except Exception as exc:
-                    result["fp32_exact"] = {"error": repr(exc)}
-            if args.batch == 1 and not args.no_batch32:
-                try:
-                    log("batch-32 leg (configs[2])")
-                    result["batch32"] = batch32_point(params, device, ref_cpu)
-                except Exception as exc:
-                    result["batch32"] = {"error": repr(exc)}
-            if args.batch == 1 and not args.no_train_step:
-                try:
-                    log("training-step leg (configs[3] per GPU)")
-                    del model, flow
-                    torch.cuda.empty_cache()
-                    result["train_step"] = train_step_point(device)
-                except Exception as exc:
-                    result["train_step"] = {"error": repr(exc)}
+                    result["cpu_baseline"] = {"error": repr(exc)}
+                if model._weights()["precision"] == 1:
+                    try:
+                        result["fp32_exact"] = fp32_reference_point(params, device, i1[:1], i2[:1], ref_cpu)
+                    except Exception as exc:
+                        result["fp32_exact"] = {"error": repr(exc)}
+                if args.batch == 1 and not args.no_batch32:
+                    try:
+                        log("batch-32 leg (configs[2])")
+                        result["batch32"] = batch32_point(params, device, ref_cpu)
+                    except Exception as exc:
+                        result["batch32"] = {"error": repr(exc)}
+                if args.batch == 1 and not args.no_train_step:
+                    try:
+                        log("training-step leg (configs[3] per GPU)")
+                        del model, flow
+                        torch.cuda.empty_cache()
+                        result["train_step"] = train_step_point(device)
+                    except Exception as exc:
+                        result["train_step"] = {"error": repr(exc)}
         print(json.dumps(result), flush=True)
     if dist is not None:
         rank_barrier()

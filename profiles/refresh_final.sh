@@ -12,7 +12,7 @@ if [ $PART = all ] || [ $PART = core ]; then
 python -m pytest tests -q -m gpu 2>&1 | tail -3 > $O/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 # the bench command under the profiler (bench.py's in_replay_us comes from this summary)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o t -- python3 bench.py $B > $O/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o t -- python3 bench.py --full $B > $O/bench_under_rocprof.log 2>&1
 cp $(find $O/prof -name "t_kernel_stats.csv" | head -1) $O/kernel_stats.csv
 python3 profiles/summarize_trace.py $(find $O/prof -name "t_kernel_trace.csv" | head -1) > $O/forward_breakdown.txt
 python3 profiles/iteration_timeline.py $(find $O/prof -name "t_kernel_trace.csv" | head -1) 100 > $O/iteration_timeline.txt
@@ -22,10 +22,10 @@ python3 profiles/chain_gaps.py $(find $O/prof -name "t_kernel_trace.csv" | head 
 rm -rf $O/prof
 # PMC passes: counters in their own runs, never together with a trace
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -o t -- python3 bench.py --steps 2 --warmup 1 --no-graph $B > /dev/null 2>&1
+  rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -o t -- python3 bench.py --full --steps 2 --warmup 1 --no-graph $B > /dev/null 2>&1
 done
 python3 profiles/pmc_traffic.py $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE > $O/pmc_traffic.json
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma -o t -- python3 bench.py --steps 2 --warmup 1 --no-graph $B > /dev/null 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma -o t -- python3 bench.py --full --steps 2 --warmup 1 --no-graph $B > /dev/null 2>&1
 python3 profiles/mfma_busy.py $O/pmc_mfma > $O/mfma_busy.json
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_mfma
 # the bench line quotes `in_replay_us`, `traffic` and the MFMA-busy fractions from the COMMITTED profile files: put this run's
@@ -35,9 +35,9 @@ R=6
 cp $O/kernel_stats.csv profiles/r${R}_final_kernel_stats.csv
 cp $O/pmc_traffic.json profiles/r${R}_final_pmc_traffic.json
 cp $O/mfma_busy.json profiles/r${R}_final_mfma_busy.json
-python bench.py 2> $O/bench_stderr.log | tail -1 > $O/bench_n1.json
-python bench.py --batch 32 --steps 5 --warmup 2 --no-train-step 2>/dev/null | tail -1 > $O/bench_batch32.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof32 -o t -- python3 bench.py --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-train-step > /dev/null 2>&1
+python bench.py --full 2> $O/bench_stderr.log | tail -1 > $O/bench_n1.json
+python bench.py --full --batch 32 --steps 5 --warmup 2 --no-train-step 2>/dev/null | tail -1 > $O/bench_batch32.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof32 -o t -- python3 bench.py --full --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-train-step > /dev/null 2>&1
 cp $(find $O/prof32 -name "t_kernel_stats.csv" | head -1) $O/kernel_stats_batch32.csv
 rm -rf $O/prof32
 python profiles/time_sizes.py 512x1024:12 640x1280:32 480x960:12 256x512:4 > $O/time_sizes.txt 2>&1
@@ -56,7 +56,7 @@ rm -rf $O/proft
 rocprofv3 --kernel-trace --output-format csv -d $O/proftg -o t -- python3 profiles/time_train_step.py --steps 3 --warmup 1 --graph > /dev/null 2>&1
 python3 profiles/train_phases.py $(find $O/proftg -name "t_kernel_trace.csv" | head -1) > $O/train_phases.txt           # one replayed step by phase
 rm -rf $O/proftg
-PRIORFLOW_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_gloo2.json
+PRIORFLOW_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_gloo2.json
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 tests/run_train_2rank.py 2>&1 | grep -E "rank|checksums" > $O/train_2rank_check.txt
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 tests/run_train_2rank.py --graphed 2>&1 | grep -E "rank|graphed" >> $O/train_2rank_check.txt
 fi
