@@ -88,6 +88,11 @@ int pf_corr_pyramid_bf16x3(const void* f1_split, const void* f2_split, float* lv
  * format of the PF_PREC_BF16X3 GEMMs.  hi = bf16(x) round-to-nearest-even, lo = bf16(x - hi). */
 int pf_split_bf16(const float* in, void* out, long rows, int C, void* stream);
 
+/* fp32 rows [rows][ld_in] (channels 0..C) -> f16 map [rows][lds_out x 128 B] (see PF_PREC_F16), fp16 round to nearest even;
+ * columns >= C are not written.  C % 4 == 0.  The context features net / inp of cnet (core/prior_raft.py:134-142) once per
+ * forward when the update blocks run in fp16 (mixed_precision: the autocast region core/prior_raft.py:190). */
+int pf_split_f16(const float* in, int ld_in, void* out, int lds_out, long rows, int C, void* stream);
+
 /* Training: the packed weight / bias gradients of several convolutions (pf_conv2d_wgrad's dw / db) added into the parameters'
  * own gradient tensors, PF_UNPACK_MAX_JOBS (16) convolutions per launch -- what optimizer-side autograd does per parameter with
  * a permute copy, a clone and two accumulation adds (train_flow.py:135 loss.backward() on the reference):
@@ -160,6 +165,13 @@ int pf_motion_prep(const float* c1a, const float* c1b, const float* g_w2c, const
                    float* xa, int xa_ld, int xa_off, float* xb, int xb_ld, int xb_off,
                    void* xa_split, int xa_lds, void* xb_split, int xb_lds,
                    float* conf, int conf_ld, int B, int H8, int W8, int C, void* stream);
+/* The same with the GRU-input tails written to f16 maps (PF_PREC_F16; xa_lds / xb_lds units of 64 channels per row) instead of
+ * split twins: the fp16 update blocks of mixed_precision (core/prior_raft.py:190, core/update.py:155,133). */
+int pf_motion_prep_f16(const float* c1a, const float* c1b, const float* g_w2c, const float* g_c2w,
+                       const float* f1a, const float* f2a, float* flow4_a, float* flow2_b,
+                       float* xa, int xa_ld, int xa_off, float* xb, int xb_ld, int xb_off,
+                       void* xa_f16, int xa_lds, void* xb_f16, int xb_lds,
+                       float* conf, int conf_ld, int B, int H8, int W8, int C, void* stream);
 
 /* Confidence stem of the ODDC motion encoder in one launch (core/update.py:177-178,193-194):
  * out[.., off_out .. off_out+16) = relu(conv3x3_{32->16}(relu(conv3x3_{8->32}(in[.., off_in .. off_in+8))))), zero padding,
@@ -169,6 +181,11 @@ int pf_motion_prep(const float* c1a, const float* c1b, const float* g_w2c, const
 int pf_conf_stem(const float* in, int ld_in, int off_in, const float* w1, const float* b1,
                  const float* w2, const float* b2, float* out, int ld_out, int off_out,
                  void* out_split, int lds_out, int B, int H8, int W8, void* stream);
+/* The same, writing an f16 map (PF_PREC_F16) instead of the split twin: the input of conv_A in the autocast region of
+ * mixed_precision (core/prior_raft.py:190, core/update.py:193-201).  Exact fp32 arithmetic as before. */
+int pf_conf_stem_f16(const float* in, int ld_in, int off_in, const float* w1, const float* b1,
+                     const float* w2, const float* b2, float* out, int ld_out, int off_out,
+                     void* out_f16, int lds_out, int B, int H8, int W8, void* stream);
 
 /* ---- update blocks ------------------------------------------------------------------------ */
 
@@ -190,6 +207,17 @@ int pf_conf_stem(const float* in, int ld_in, int off_in, const float* w1, const 
 #define PF_PREC_F32 0     /* exact fp32 MFMA; weights fp32 [Cout_pad][KH*KW][Cin_pad]                 */
 #define PF_PREC_BF16X3 1  /* 3-pass bf16 split (hi*hi + hi*lo + lo*hi), fp32 accumulate; weights     *
                            * pre-split: [Cout_pad][KH*KW][Cin_pad/32] x {bf16 hi[32], bf16 lo[32]}  */
+#define PF_PREC_F16 2     /* single-pass fp16 operands, fp32 accumulate, bias / epilogue / outputs fp32: the update blocks
+                           * under CUDA autocast (mixed_precision, core/prior_raft.py:190; core/update.py).  Weights fp16
+                           * [Cout_pad][KH*KW][Cin_pad64] (Cin_pad64 = c0 + c1 rounded up to 64).  Operands are F16 MAPS only:
+                           * in0_split / in1_split / out_split / aux_split then denote channel-last fp16 rows of lds x 128 bytes
+                           * (64 channels per unit, channel c at byte 2c of the row, zero past the logical width -- a padded
+                           * float16 tensor [rows][lds * 64]); fp16 = round to nearest even of the producer's fp32 value.
+                           * off0 / off1 (and c0 with in1) must be multiples of 64, a last segment ending inside a 64-channel
+                           * unit must end at its row's end, every group of a launch is F16, and the launch must be one the
+                           * all-DMA kernel takes (stride-1 3x3 / 1x5 / 5x1, no in_scale / stats_out): PF_ERR_BAD_SHAPE /
+                           * PF_ERR_BAD_ARG otherwise, never a fallback.  pf_conv2d_tile / _roles / _stats_blocks report
+                           * the plan of an F16 launch like any other. */
 
 /* One stride-1 "same" convolution on channel-last activations as an implicit GEMM on the
  * matrix cores (nn.Conv2d forwards of core/update.py:6-14, 35-60, 81-99, 117-136, 139-201).
@@ -272,6 +300,9 @@ typedef struct pf_combine_conv_desc {
 } pf_combine_conv_desc;
 /* ngroups = 1 | 2: branch A and branch B of an iteration in one launch (grid.y = group). */
 int pf_dccl_combine_conv1x1(const pf_combine_conv_desc* descs, int ngroups, int B, int H8, int W8, void* stream);
+/* The same launch (bf16x3 arithmetic) with out_split an f16 map (PF_PREC_F16, lds_out units of 64 channels): convc1's output
+ * as the operand of the fp16 convc2 under mixed_precision (core/prior_raft.py:190, core/update.py:185-186 / :92-93). */
+int pf_dccl_combine_conv1x1_f16(const pf_combine_conv_desc* descs, int ngroups, int B, int H8, int W8, void* stream);
 
 /* Launch `ngroups` (1..4) same-geometry convolutions in ONE kernel (grid.z = group):
  * branch A and branch B of an iteration run side by side.  H8, W8 = OUTPUT map size. */
@@ -328,6 +359,10 @@ typedef struct pf_direct_desc {
 } pf_direct_desc;
 int pf_conv2d_direct_group(const pf_direct_desc* descs, int n, int cin, int cout, int kh, int kw, int relu,
                            int B, int H8, int W8, void* stream);
+/* The same with out_split an f16 map (PF_PREC_F16, lds_out units of 64 channels): the 7x7 flow stems' outputs as operands of
+ * the fp16 3x3s under mixed_precision (core/prior_raft.py:190, core/update.py:187-191 / :94-95). */
+int pf_conv2d_direct_group_f16(const pf_direct_desc* descs, int n, int cin, int cout, int kh, int kw, int relu,
+                               int B, int H8, int W8, void* stream);
 
 /* Small-Cin convolution with stride 1|2 from channel-last or NCHW input (the encoders' 7x7/2 3->64
  * stem, core/extractor.py:112,144; same kernel family as pf_conv2d_direct).  Hout/Wout = OUTPUT map;

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PRIORFLOW_LIB") or os.path.join(_HERE, "lib", "libpriorflow_hip.so")
 
 EPI_LINEAR, EPI_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_TANH_RELU, EPI_RELU_RES, EPI_MASK, EPI_ADD = 0, 1, 2, 3, 4, 5, 6, 7
-PREC_F32, PREC_BF16X3 = 0, 1
+PREC_F32, PREC_BF16X3, PREC_F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 
 _fp = C.c_void_p
@@ -90,6 +90,7 @@ _SIGNATURES = {
     "pf_corr_pyramid": [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp],
     "pf_corr_pyramid_bf16x3": [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp],
     "pf_split_bf16": [_fp, _fp, C.c_long, _i, _fp],
+    "pf_split_f16": [_fp, _i, _fp, _i, C.c_long, _i, _fp],
     "pf_enc_stem": [_fp, _fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _fp],
     "pf_debug_dirty_lds": [C.c_uint, _fp],
     "pf_gru_dx_finish": [_fp, _i, _fp, _i, _fp, _i, _fp, _i, _fp, _i, C.c_long, _i, _i, _fp],
@@ -105,14 +106,18 @@ _SIGNATURES = {
     "pf_dccl_combine": [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp],
     "pf_warp_gcorr": [_fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _i, _fp],
     "pf_conf_stem": [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _fp],
+    "pf_conf_stem_f16": [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _fp],
     "pf_motion_prep": [_fp] * 9 + [_i, _i, _fp, _i, _i, _fp, _i, _fp, _i, _fp, _i, _i, _i, _i, _i, _fp],
+    "pf_motion_prep_f16": [_fp] * 9 + [_i, _i, _fp, _i, _i, _fp, _i, _fp, _i, _fp, _i, _i, _i, _i, _i, _fp],
     "pf_conv2d": [C.POINTER(ConvDesc), _i, _i, _i, _i, _fp],
     "pf_dccl_combine_conv1x1": [C.POINTER(CombineConvDesc), _i, _i, _i, _i, _fp],
+    "pf_dccl_combine_conv1x1_f16": [C.POINTER(CombineConvDesc), _i, _i, _i, _i, _fp],
     "pf_conv2d_tile": [C.POINTER(ConvDesc), _i, _i, _i, _i],
     "pf_conv2d_stats_blocks": [C.POINTER(ConvDesc), _i, _i, _i, _i],
     "pf_conv2d_roles": [C.POINTER(ConvDesc), _i, _i, _i, _i],
     "pf_conv2d_direct": [_fp, _i, _i, _i, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp],
     "pf_conv2d_direct_group": [C.POINTER(DirectDesc), _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp],
+    "pf_conv2d_direct_group_f16": [C.POINTER(DirectDesc), _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp],
     "pf_conv2d_small": [_fp, _i, _i, _i, _i, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp],
     "pf_channel_stats": [_fp, _i, _i, _i, C.c_float, _fp, _fp, _fp, _i, _fp],
     "pf_channel_stats_final": [_fp, _i, _i, _i, _i, C.c_float, _fp, _fp, _fp],
@@ -163,6 +168,31 @@ def _twin(t: Optional[torch.Tensor]):
     if t.dtype != torch.bfloat16 or t.dim() != 4 or tuple(t.shape[2:]) != (2, 32) or not t.is_contiguous():
         raise PfError("a split twin is a contiguous bfloat16 tensor [rows, chunks, 2, 32]")
     return C.c_void_p(t.data_ptr()), t.shape[1]
+
+
+def is_f16_map(t: Optional[torch.Tensor]) -> bool:
+    """An f16 map (PF_PREC_F16 operand, include/priorflow_hip.h): contiguous float16 [rows, lds * 64] (``engine.f16_map``)."""
+    return t is not None and t.dtype == torch.float16
+
+
+def _opmap(t: Optional[torch.Tensor]):
+    """(pointer, 128-byte units per row, is_f16) of a split twin or an f16 map, or (None, 0, False)."""
+    if t is None:
+        return None, 0, False
+    if is_f16_map(t):
+        if t.dim() != 2 or t.shape[1] % 64 or not t.is_contiguous():
+            raise PfError("an f16 map is a contiguous float16 tensor [rows, lds * 64]")
+        return C.c_void_p(t.data_ptr()), t.shape[1] // 64, True
+    p, n = _twin(t)
+    return p, n, False
+
+
+def _one_form(*maps) -> bool:
+    """True when the given operand buffers are f16 maps, False for split twins; a mix is an error."""
+    kinds = {f for p, _, f in maps if p is not None}
+    if len(kinds) > 1:
+        raise PfError("split twins and f16 maps mixed in one launch")
+    return kinds == {True}
 
 
 class PfLib:
@@ -283,24 +313,29 @@ class PfLib:
 
     def conf_stem(self, x, off_in, w1, b1, w2, b2, out, off_out, B, H8, W8, out_split=None):
         """relu(conv3x3 32->16(relu(conv3x3 8->32(x)))) in one launch (core/update.py:193-194); w*: [9*Cin][Cout].
-        out_split: optional split twin of `out` written at the same channel offset (`out` may then be None)."""
+        out_split: optional split twin -- or f16 map (pf_conf_stem_f16) -- of `out` written at the same channel offset (`out` may
+        then be None)."""
         self._chk(x, w1, b1, w2, b2, out)
-        sp, lds = _twin(out_split)
-        self._rc(self._dll.pf_conf_stem(_ptr(x), x.shape[-1], off_in, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
-                                        _ptr(out), 0 if out is None else out.shape[-1], off_out, sp, lds,
-                                        B, H8, W8, self._stream(x)), "pf_conf_stem")
+        o = _opmap(out_split)
+        fn = "pf_conf_stem_f16" if _one_form(o) else "pf_conf_stem"
+        self._rc(getattr(self._dll, fn)(_ptr(x), x.shape[-1], off_in, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
+                                        _ptr(out), 0 if out is None else out.shape[-1], off_out, o[0], o[1],
+                                        B, H8, W8, self._stream(x)), fn)
 
     def motion_prep(self, c1a, c1b, g_w2c, g_c2w, f1a, f2a, flow4_a, flow2_b, conf, xa=None, xa_off=0, xb=None, xb_off=0,
                     xa_split=None, xb_split=None):
         """One launch for flow_prep x2 + flo_rotate + warp_gcorr x2 (core/prior_raft.py:171-182), bit-identical to them.
-        xa_split / xb_split: optional split twins of the GRU input buffers (tails written at xa_off / xb_off)."""
+        xa_split / xb_split: optional split twins -- or f16 maps, both alike (pf_motion_prep_f16) -- of the GRU input buffers
+        (tails written at xa_off / xb_off)."""
         self._chk(c1a, c1b, g_w2c, g_c2w, f1a, f2a, flow4_a, flow2_b, conf, xa, xb)
         B, _, H, W = c1a.shape
-        (sa, la), (sb, lb) = _twin(xa_split), _twin(xb_split)
-        self._rc(self._dll.pf_motion_prep(
+        ma, mb = _opmap(xa_split), _opmap(xb_split)
+        (sa, la), (sb, lb) = ma[:2], mb[:2]
+        fn = "pf_motion_prep_f16" if _one_form(ma, mb) else "pf_motion_prep"
+        self._rc(getattr(self._dll, fn)(
             _ptr(c1a), _ptr(c1b), _ptr(g_w2c), _ptr(g_c2w), _ptr(f1a), _ptr(f2a), _ptr(flow4_a), _ptr(flow2_b),
             _ptr(xa), 0 if xa is None else xa.shape[-1], xa_off, _ptr(xb), 0 if xb is None else xb.shape[-1], xb_off,
-            sa, la, sb, lb, _ptr(conf), conf.shape[-1], B, H, W, f1a.shape[-1], self._stream(c1a)), "pf_motion_prep")
+            sa, la, sb, lb, _ptr(conf), conf.shape[-1], B, H, W, f1a.shape[-1], self._stream(c1a)), fn)
 
     # ---- correlation -------------------------------------------------------------------------
     def corr_pyramid(self, f1, f2, levels, B, H8, W8):
@@ -316,6 +351,16 @@ class PfLib:
             raise PfError("split_bf16: out must be contiguous bfloat16 with 2x the elements of x")
         self._rc(self._dll.pf_split_bf16(_ptr(x), C.c_void_p(out.data_ptr()), x.shape[0], x.shape[-1],
                                          self._stream(x)), "pf_split_bf16")
+        return out
+
+    def split_f16(self, x, out):
+        """x fp32 rows [rows, C] (a column slice of wider rows is fine) -> f16 map out float16 [rows, lds * 64], fp16 round to
+        nearest even; the map's columns >= C are left as they are (zero)."""
+        self._chk_rows(x)
+        p, lds, f16 = _opmap(out)
+        if not f16 or out.shape[0] != x.shape[0]:
+            raise PfError("split_f16: out must be an f16 map with the rows of x")
+        self._rc(self._dll.pf_split_f16(_ptr(x), x.stride(0), p, lds, x.shape[0], x.shape[1], self._stream(x)), "pf_split_f16")
         return out
 
     def pack_conv_weights(self, w0, b0=None, w1=None, b1=None, mode=0, cin_rot=0, cout_pad_to=128):
@@ -400,13 +445,16 @@ class PfLib:
     def dccl_combine_conv1x1(self, items, B, H8, W8):
         """items: 1 or 2 tuples (own, raw, g_back, conv, out, off_out[, out_split]) with `conv` a packed bf16x3 1x1 324->256
         engine.Conv: out[.., off_out:off_out+256] = relu(conv(own + rotate_back(raw))) without materialising the sum.
-        out_split: optional split twin of `out` (`out` may then be None)."""
+        out_split: optional split twin -- or f16 map, in every item alike (pf_dccl_combine_conv1x1_f16) -- of `out` (`out` may
+        then be None)."""
         arr = (CombineConvDesc * len(items))()
         keep = []
-        for d, item in zip(arr, items):
+        maps = [_opmap(item[6] if len(item) > 6 else None) for item in items]
+        fn = "pf_dccl_combine_conv1x1_f16" if _one_form(*maps) else "pf_dccl_combine_conv1x1"
+        for d, item, m in zip(arr, items, maps):
             own, raw, g_back, conv, out, off_out = item[:6]
             out_split = item[6] if len(item) > 6 else None
-            d.out_split, d.lds_out = _twin(out_split)
+            d.out_split, d.lds_out = m[:2]
             self._chk(own, raw, g_back, conv.b, out)
             if conv.precision != PREC_BF16X3 or (conv.kh, conv.kw, conv.cin, conv.cout) != (1, 1, 324, 256):
                 raise PfError("dccl_combine_conv1x1 needs the bf16x3 packing of a 1x1 324(352)->256 convolution")
@@ -415,8 +463,7 @@ class PfLib:
             d.out = out.data_ptr() if out is not None else None
             d.ld_out, d.off_out, d.cout = (out.shape[-1] if out is not None else 0), off_out, conv.cout
             keep.append((own, raw, g_back, conv, out, out_split))
-        self._rc(self._dll.pf_dccl_combine_conv1x1(arr, len(items), B, H8, W8, self._stream(items[0][0])),
-                 "pf_dccl_combine_conv1x1")
+        self._rc(getattr(self._dll, fn)(arr, len(items), B, H8, W8, self._stream(items[0][0])), fn)
 
     def warp_gcorr(self, f1, f2, coords, add_grid, dst, dst_off):
         self._chk(f1, f2, coords, dst)
@@ -460,17 +507,20 @@ class PfLib:
 
     def conv2d_direct_group(self, problems, cin, cout, kh, kw, relu, B, H8, W8):
         """problems: 1..4 tuples (x, off_in, weight, bias, out, off_out[, out_split]) of one shape -> one launch.
-        out_split: optional split twin of `out` (7x7 2 -> C stems; `out` may then be None)."""
+        out_split: optional split twin -- or f16 map, in every problem alike (pf_conv2d_direct_group_f16) -- of `out` (7x7 2 -> C
+        stems; `out` may then be None)."""
         arr = (DirectDesc * len(problems))()
-        for d, item in zip(arr, problems):
+        maps = [_opmap(item[6] if len(item) > 6 else None) for item in problems]
+        fn = "pf_conv2d_direct_group_f16" if _one_form(*maps) else "pf_conv2d_direct_group"
+        for d, item, m in zip(arr, problems, maps):
             x, off_in, weight, bias, out, off_out = item[:6]
             self._chk(x, weight, bias, out)
             d.in_, d.ld_in, d.off_in = _ptr(x), x.shape[-1], off_in
             d.weight, d.bias = _ptr(weight), _ptr(bias)
             d.out, d.ld_out, d.off_out = _ptr(out), (out.shape[-1] if out is not None else 0), off_out
-            d.out_split, d.lds_out = _twin(item[6] if len(item) > 6 else None)
-        self._rc(self._dll.pf_conv2d_direct_group(arr, len(problems), cin, cout, kh, kw, int(relu), B, H8, W8,
-                                                  self._stream(problems[0][0])), "pf_conv2d_direct_group")
+            d.out_split, d.lds_out = m[:2]
+        self._rc(getattr(self._dll, fn)(arr, len(problems), cin, cout, kh, kw, int(relu), B, H8, W8,
+                                        self._stream(problems[0][0])), fn)
 
     def conv2d_small(self, x, nchw, off_in, cin, weight, bias, out, off_out, cout, kh, kw, stride, relu,
                      B, Hout, Wout):

@@ -140,7 +140,7 @@ static inline int pf_small_conv_fill(PfDirectConvArgs& a, const float* in, int n
     a.w = weight; a.bias = bias; a.out = out; a.ld_out = ld_out; a.c_out_off = off_out; a.Cout = cout;
     a.B = B; a.H = Hout; a.W = Wout; a.KH = kh; a.KW = kw; a.relu = relu;
     a.stride = stride; a.nchw = nchw; a.Hin = Hout * stride; a.Win = Wout * stride;
-    a.out_split = nullptr; a.lds_out = 0;
+    a.out_split = nullptr; a.lds_out = 0; a.out_f16 = 0;
     return PF_OK;
 }
 
@@ -155,8 +155,8 @@ extern "C" int pf_conv2d_direct(const float* in, int ld_in, int off_in, int cin,
     return PF_DIRECT_CONV_LAUNCH(a, (long)B * H8 * W8 * cout, stream);
 }
 
-extern "C" int pf_conv2d_direct_group(const pf_direct_desc* descs, int n, int cin, int cout, int kh, int kw, int relu,
-                                      int B, int H8, int W8, void* stream) {
+static int pf_direct_group_impl(const pf_direct_desc* descs, int n, int cin, int cout, int kh, int kw, int relu,
+                                int B, int H8, int W8, int f16, void* stream) {
     PF_REQUIRE(descs && n >= 1 && n <= 4);
     PfDirectConvArgs a[4];
     for (int i = 0; i < n; ++i) {
@@ -165,13 +165,23 @@ extern "C" int pf_conv2d_direct_group(const pf_direct_desc* descs, int n, int ci
         const int rc = pf_small_conv_fill(a[i], d.in, 0, d.ld_in, d.off_in, cin, d.weight, d.bias, d.out,
                                           d.out ? d.ld_out : d.off_out + cout, d.off_out, cout, kh, kw, 1, relu, B, H8, W8);
         if (rc != PF_OK) return rc;
-        PF_REQUIRE_SHAPE(!d.out_split || (d.off_out % 8 == 0 && d.off_out + cout <= d.lds_out * 32));
-        a[i].out_split = d.out_split; a[i].lds_out = d.lds_out;
+        PF_REQUIRE_SHAPE(!d.out_split || (d.off_out % 8 == 0 && d.off_out + cout <= d.lds_out * (f16 ? 64 : 32)));
+        a[i].out_split = d.out_split; a[i].lds_out = d.lds_out; a[i].out_f16 = f16;
         for (int k = 0; k < i; ++k)       // outputs of a group are written concurrently: they must not overlap
             PF_REQUIRE(!(descs[k].out == d.out && descs[k].out_split == d.out_split &&
                          descs[k].off_out < d.off_out + cout && d.off_out < descs[k].off_out + cout));
     }
     return PF_DIRECT_CONV_GROUP_LAUNCH(a, n, (long)B * H8 * W8 * cout, stream);
+}
+
+extern "C" int pf_conv2d_direct_group(const pf_direct_desc* descs, int n, int cin, int cout, int kh, int kw, int relu,
+                                      int B, int H8, int W8, void* stream) {
+    return pf_direct_group_impl(descs, n, cin, cout, kh, kw, relu, B, H8, W8, 0, stream);
+}
+
+extern "C" int pf_conv2d_direct_group_f16(const pf_direct_desc* descs, int n, int cin, int cout, int kh, int kw, int relu,
+                                          int B, int H8, int W8, void* stream) {
+    return pf_direct_group_impl(descs, n, cin, cout, kh, kw, relu, B, H8, W8, 1, stream);
 }
 
 extern "C" int pf_conv2d_small(const float* in, int nchw, int ld_in, int off_in, int cin,
@@ -214,6 +224,13 @@ extern "C" int pf_split_bf16(const float* in, void* out, long rows, int C, void*
     PF_REQUIRE_SHAPE(rows > 0 && C > 0 && C % 32 == 0);
     PfSplitArgs a; a.in = in; a.out = (unsigned short*)out; a.rows = rows; a.C = C;
     return PF_LAUNCH(split_bf16, a, rows * (C / 4), stream);
+}
+
+extern "C" int pf_split_f16(const float* in, int ld_in, void* out, int lds_out, long rows, int C, void* stream) {
+    PF_REQUIRE(in && out && (const void*)in != out);
+    PF_REQUIRE_SHAPE(rows > 0 && C > 0 && C % 4 == 0 && ld_in >= C && ld_in % 4 == 0 && lds_out * 64 >= C);
+    PfSplitF16Args a; a.in = in; a.out = (unsigned short*)out; a.rows = rows; a.C = C; a.ld_in = ld_in; a.lds = lds_out;
+    return PF_LAUNCH(split_f16, a, rows * (C / 4), stream);
 }
 
 static int pf_pack_job_args(const float* w0, int cout0, const float* w1, int cout1, const float* b0, const float* b1,
@@ -544,3 +561,56 @@ static inline int pf_warp_gcorr_fill(PfWarpGcorrArgs& a, const float* f1, const 
     a.B = B; a.H = H8; a.W = W8; a.C = C; a.add_grid = add_grid;
     return PF_OK;
 }
+
+#if !defined(__HIPCC__)
+// Host build (tests/emu): the f16-map forms of the motion-input producers as their fp32 forms into a temporary + pf_f16_put
+// (the device kernels write the same values straight from registers).  The fused combine + 1x1 has no host statement in either
+// operand form.
+#include <stdlib.h>
+extern "C" int pf_conf_stem_f16(const float* in, int ld_in, int off_in, const float* w1, const float* b1,
+                                const float* w2, const float* b2, float* out, int ld_out, int off_out,
+                                void* out_f16, int lds_out, int B, int H8, int W8, void* stream) {
+    PF_REQUIRE(out || out_f16);
+    PF_REQUIRE_SHAPE(B > 0 && H8 > 0 && W8 > 0 && off_out >= 0 && (!out_f16 || off_out + 16 <= lds_out * 64));
+    const long rows = (long)B * H8 * W8;
+    float* t = (float*)malloc(sizeof(float) * rows * 16);
+    if (!t) return PF_ERR_BAD_ARG;
+    int rc = pf_conf_stem(in, ld_in, off_in, w1, b1, w2, b2, t, 16, 0, nullptr, 0, B, H8, W8, stream);
+    for (long r = 0; rc == PF_OK && r < rows; ++r)
+        for (int c = 0; c < 16; ++c) {
+            if (out) out[r * ld_out + off_out + c] = t[r * 16 + c];
+            if (out_f16) pf_f16_put(out_f16, r, lds_out, off_out + c, t[r * 16 + c]);
+        }
+    free(t);
+    return rc;
+}
+
+extern "C" int pf_motion_prep_f16(const float* c1a, const float* c1b, const float* g_w2c, const float* g_c2w,
+                                  const float* f1a, const float* f2a, float* flow4_a, float* flow2_b,
+                                  float* xa, int xa_ld, int xa_off, float* xb, int xb_ld, int xb_off,
+                                  void* xa_f16, int xa_lds, void* xb_f16, int xb_lds,
+                                  float* conf, int conf_ld, int B, int H8, int W8, int C, void* stream) {
+    PF_REQUIRE_SHAPE(B > 0 && H8 > 0 && W8 > 0);
+    PF_REQUIRE(!xa_f16 || (xa_off >= 0 && xa_off + 4 <= xa_lds * 64));
+    PF_REQUIRE(!xb_f16 || (xb_off >= 0 && xb_off + 2 <= xb_lds * 64));
+    const long rows = (long)B * H8 * W8;
+    float* t = (float*)malloc(sizeof(float) * rows * 6);      // [rows][4] tails of xa, then [rows][2] of xb
+    if (!t) return PF_ERR_BAD_ARG;
+    int rc = pf_motion_prep(c1a, c1b, g_w2c, g_c2w, f1a, f2a, flow4_a, flow2_b, t, 4, 0, t + rows * 4, 2, 0,
+                            nullptr, 0, nullptr, 0, conf, conf_ld, B, H8, W8, C, stream);
+    for (long r = 0; rc == PF_OK && r < rows; ++r) {
+        for (int c = 0; c < 4; ++c) {
+            if (xa) xa[r * xa_ld + xa_off + c] = t[r * 4 + c];
+            if (xa_f16) pf_f16_put(xa_f16, r, xa_lds, xa_off + c, t[r * 4 + c]);
+        }
+        for (int c = 0; c < 2; ++c) {
+            if (xb) xb[r * xb_ld + xb_off + c] = t[rows * 4 + r * 2 + c];
+            if (xb_f16) pf_f16_put(xb_f16, r, xb_lds, xb_off + c, t[rows * 4 + r * 2 + c]);
+        }
+    }
+    free(t);
+    return rc;
+}
+
+extern "C" int pf_dccl_combine_conv1x1_f16(const pf_combine_conv_desc*, int, int, int, int, void*) { return PF_ERR_BAD_SHAPE; }
+#endif

@@ -16,17 +16,21 @@ static int conv_prepare(const pf_conv_desc* descs, int ngroups, int B, int H8, i
         const pf_conv_desc& d = descs[i];
         if ((!d.in0 && !d.in0_split) || !d.weight || !d.bias || (!d.out && !d.out_split)) return PF_ERR_BAD_ARG;
         if (d.c0 <= 0 || d.c1 < 0 || (d.c1 > 0 && !d.in1 && !d.in1_split)) return PF_ERR_BAD_ARG;
-        // split twins (include/priorflow_hip.h): bf16x3 arithmetic, chunk-aligned slices that fit their rows
-        if ((d.in0_split || d.in1_split || d.out_split || d.aux_split) && d.precision != PF_PREC_BF16X3) return PF_ERR_BAD_ARG;
-        if (d.in0_split && ((d.off0 & 31) || d.lds0 * 32 < d.off0 + d.c0)) return PF_ERR_BAD_SHAPE;
-        if (d.in1_split && d.c1 > 0 && ((d.off1 & 31) || (d.c0 & 31) || d.lds1 * 32 < d.off1 + d.c1)) return PF_ERR_BAD_SHAPE;
-        // The all-DMA kernel copies whole 32-channel chunks: a slice that ends inside a chunk must end at the END OF THE ROW, where
-        // the twin's columns past the logical width are zero by contract (anywhere else it would multiply a neighbour's live
+        // split twins (include/priorflow_hip.h): bf16x3 arithmetic, chunk-aligned slices that fit their rows; f16 maps (PF_PREC_F16):
+        // the same with 64-channel chunks, and the operands exist in that form only
+        const bool f16 = d.precision == PF_PREC_F16;
+        const int cpc = f16 ? 64 : 32, cm = cpc - 1;         // channels per 128-byte chunk of an operand row
+        if ((d.in0_split || d.in1_split || d.out_split || d.aux_split) && d.precision != PF_PREC_BF16X3 && !f16) return PF_ERR_BAD_ARG;
+        if (f16 && (!d.in0_split || (d.c1 > 0 && !d.in1_split))) return PF_ERR_BAD_ARG;
+        if (d.in0_split && ((d.off0 & cm) || d.lds0 * cpc < d.off0 + d.c0)) return PF_ERR_BAD_SHAPE;
+        if (d.in1_split && d.c1 > 0 && ((d.off1 & cm) || (d.c0 & cm) || d.lds1 * cpc < d.off1 + d.c1)) return PF_ERR_BAD_SHAPE;
+        // The all-DMA kernel copies whole chunks: a slice that ends inside a chunk must end at the END OF THE ROW, where
+        // the operand row's columns past the logical width are zero by contract (anywhere else it would multiply a neighbour's live
         // columns -- possibly Inf / NaN -- by the zero-padded weights)
-        if (d.in0_split && d.c1 == 0 && (d.c0 & 31) && d.off0 + ((d.c0 + 31) & ~31) != d.lds0 * 32) return PF_ERR_BAD_SHAPE;
-        if (d.in1_split && d.c1 > 0 && (d.c1 & 31) && d.off1 + ((d.c1 + 31) & ~31) != d.lds1 * 32) return PF_ERR_BAD_SHAPE;
+        if (d.in0_split && d.c1 == 0 && (d.c0 & cm) && d.off0 + ((d.c0 + cm) & ~cm) != d.lds0 * cpc) return PF_ERR_BAD_SHAPE;
+        if (d.in1_split && d.c1 > 0 && (d.c1 & cm) && d.off1 + ((d.c1 + cm) & ~cm) != d.lds1 * cpc) return PF_ERR_BAD_SHAPE;
         if (d.out_split && ((d.off_out & 31) || d.lds_out <= 0)) return PF_ERR_BAD_SHAPE;
-        if (d.aux_split && d.lds_aux * 32 < 128) return PF_ERR_BAD_SHAPE;
+        if (d.aux_split && d.lds_aux * cpc < 128) return PF_ERR_BAD_SHAPE;
         if (d.pre && (d.off_pre < 0 || d.off_pre + d.cout > d.ld_pre)) return PF_ERR_BAD_SHAPE;
         if ((d.in0_split != nullptr) != (f.in0_split != nullptr) || (d.c1 > 0 && (d.in1_split != nullptr) != (d.in0_split != nullptr)))
             return PF_ERR_BAD_ARG;              // every group and both segments agree on the operand form
@@ -47,10 +51,10 @@ static int conv_prepare(const pf_conv_desc* descs, int ngroups, int B, int H8, i
         if (d.stride != f.stride || (d.stride != 1 && d.stride != 2)) return PF_ERR_BAD_SHAPE;
         if ((d.in_scale == nullptr) != (d.in_shift == nullptr)) return PF_ERR_BAD_ARG;
         if (d.epilogue == PF_EPI_TANH_RELU && (d.cout != 256 || (!d.aux_out && !d.aux_split) || (d.aux_out && d.ld_aux < 128))) return PF_ERR_BAD_ARG;
-        if (d.precision != f.precision || (d.precision != PF_PREC_F32 && d.precision != PF_PREC_BF16X3))
+        if (d.precision != f.precision || (d.precision != PF_PREC_F32 && d.precision != PF_PREC_BF16X3 && !f16))
             return PF_ERR_BAD_ARG;
         const int out_w = (d.epilogue == PF_EPI_GRU_ZR || d.epilogue == PF_EPI_TANH_RELU) ? 128 : d.cout;
-        if (d.off_out < 0 || (d.out && d.off_out + out_w > d.ld_out) || (d.out_split && d.off_out + out_w > d.lds_out * 32))
+        if (d.off_out < 0 || (d.out && d.off_out + out_w > d.ld_out) || (d.out_split && d.off_out + out_w > d.lds_out * cpc))
             return PF_ERR_BAD_ARG;
         if (d.epilogue == PF_EPI_GRU_ZR && (d.cout != 256 || !d.h || (!d.aux_out && !d.aux_split) || (d.aux_out && d.ld_aux < 128) || d.ld_h < 128))
             return PF_ERR_BAD_ARG;
@@ -62,8 +66,9 @@ static int conv_prepare(const pf_conv_desc* descs, int ngroups, int B, int H8, i
     for (int i = ngroups; i < MAX_GROUPS; ++i) grp.d[i] = descs[0];
     g.H = H8; g.W = W8; g.N = H8 * W8; g.M = B * H8 * W8;
     g.kh = f.kh; g.kw = f.kw; g.taps = f.kh * f.kw;
-    g.cin_pad = (f.c0 + f.c1 + KC - 1) / KC * KC;
-    g.nchunks = g.cin_pad / KC;
+    const int kc = f.precision == PF_PREC_F16 ? 64 : KC;     // channels per K-step of the kernel (F16: all-DMA kernel only)
+    g.cin_pad = (f.c0 + f.c1 + kc - 1) / kc * kc;
+    g.nchunks = g.cin_pad / kc;
     g.stride = f.stride; g.Hin = H8 * f.stride; g.Win = W8 * f.stride; g.Nin = g.Hin * g.Win;
     if (f.co_groups < 0 || f.co_groups > MAX_GROUPS) return PF_ERR_BAD_ARG;
     return PF_OK;
@@ -79,7 +84,7 @@ static int conv_prepare(const pf_conv_desc* descs, int ngroups, int B, int H8, i
 static int conv_tile(const ConvGeom& g, int ngroups, int max_cout, int precision) {
     const bool halo_shape = (g.kh == 3 && g.kw == 3) || (g.kh == 1 && g.kw == 5) || (g.kh == 5 && g.kw == 1) ||
                             (g.kh == 4 && g.kw == 4) || (g.kh == 1 && g.kw == 1);
-    if (precision == PF_PREC_BF16X3 && halo_shape && g.stride == 1) {
+    if ((precision == PF_PREC_BF16X3 || precision == PF_PREC_F16) && halo_shape && g.stride == 1) {
         const long B = g.M / g.N;
         const long tiles4 = B * ((g.H + 3) / 4) * ((g.W + 31) / 32), tiles8 = B * ((g.H + 7) / 8) * ((g.W + 31) / 32);
         const long wgs128 = tiles4 * ngroups * ((max_cout + 127) / 128);
@@ -100,6 +105,7 @@ static int conv_tile(const ConvGeom& g, int ngroups, int max_cout, int precision
 // Pre-split operands (pf_conv_desc.in0_split): which tile the all-DMA kernel takes -- 0: not applicable (fp32 operands,
 // a shape / option it does not implement), else the pf_conv2d_roles code (1: 128-px tile, 2: 256 px x 64 channels).
 // (The engine's PRIORFLOW_PRESPLIT=0 is the A/B against the register-staged kernels: it hands over fp32 operands.)
+// PF_PREC_F16 exists on this kernel only: a launch it does not take is an error for the caller (f16_plan), never a fallback.
 static int conv_dma_choice(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout, int tile_id) {
     if (!grp.d[0].in0_split || tile_id < 3 || tile_id == 7) return 0;
     const bool shape = (g.kh == 3 && g.kw == 3) || (g.kh == 1 && g.kw == 5) || (g.kh == 5 && g.kw == 1);
@@ -115,11 +121,18 @@ static int conv_dma_choice(const ConvGroups& grp, int ngroups, const ConvGeom& g
 }
 
 
+// PF_PREC_F16 launch: PF_OK when the all-DMA kernel takes it, PF_ERR_BAD_SHAPE otherwise (any other precision: PF_OK)
+static int f16_plan(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout, int tile) {
+    if (grp.d[0].precision != PF_PREC_F16) return PF_OK;
+    return conv_dma_choice(grp, ngroups, g, max_cout, tile) ? PF_OK : PF_ERR_BAD_SHAPE;
+}
+
 extern "C" int pf_conv2d_tile(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8) {
     ConvGroups grp; ConvGeom g; int max_cout;
     const int rc = conv_prepare(descs, ngroups, B, H8, W8, grp, g, max_cout);
     if (rc != PF_OK) return rc;
     const int tile = conv_tile(g, ngroups + descs[0].co_groups, max_cout, descs[0].precision);
+    if (const int e = f16_plan(grp, ngroups, g, max_cout, tile)) return e;
     // 6: the weights-stationary kernel of the encoders' 3x3 64 -> 64 convolutions (pf_enc_conv.hip): its statistics partials are
     // per (segment, row phase, strip) -- pf_conv2d_stats_blocks
     return ((tile == 5 || tile == 3) && pf_enc_conv64_applies(grp, ngroups, g, max_cout)) ? 6 : tile;
@@ -130,6 +143,7 @@ extern "C" int pf_conv2d_stats_blocks(const pf_conv_desc* descs, int ngroups, in
     const int rc = conv_prepare(descs, ngroups, B, H8, W8, grp, g, max_cout);
     if (rc != PF_OK) return rc;
     const int tile = conv_tile(g, ngroups + descs[0].co_groups, max_cout, descs[0].precision);
+    if (const int e = f16_plan(grp, ngroups, g, max_cout, tile)) return e;
     const bool split = descs[0].precision == PF_PREC_BF16X3;
     if ((tile == 5 || tile == 3) && pf_enc_conv64_applies(grp, ngroups, g, max_cout)) return pf_enc_conv64_stats_blocks(g);
     if (tile >= 3 && tile != 7) { const int th = (tile == 5 || tile == 8) ? 8 : 4; return ((g.H + th - 1) / th) * ((g.W + 31) / 32); }
@@ -142,6 +156,7 @@ extern "C" int pf_conv2d_roles(const pf_conv_desc* descs, int ngroups, int B, in
     const int rc = conv_prepare(descs, ngroups, B, H8, W8, grp, g, max_cout);
     if (rc != PF_OK) return rc;
     const int tile = conv_tile(g, ngroups + descs[0].co_groups, max_cout, descs[0].precision);
+    if (const int e = f16_plan(grp, ngroups, g, max_cout, tile)) return e;
     if (const int dma = conv_dma_choice(grp, ngroups, g, max_cout, tile)) return 16 + dma;
     return (tile == 3 || tile == 4) ? pf_conv_ws_choice(grp, ngroups, g, max_cout) : 0;
 }
@@ -153,6 +168,7 @@ extern "C" int pf_conv2d(const pf_conv_desc* descs, int ngroups, int B, int H8, 
     hipStream_t s = (hipStream_t)stream;
     const bool split = descs[0].precision == PF_PREC_BF16X3;
     const int tile_id = conv_tile(g, ngroups + descs[0].co_groups, max_cout, descs[0].precision);
+    if (const int e = f16_plan(grp, ngroups, g, max_cout, tile_id)) return e;
     const bool generic = tile_id < 3 || tile_id == 7;
     for (int i = 0; i < ngroups; ++i) {     // the input affine is implemented by the halo kernel only; the fused statistics by the
         if (descs[i].in_scale && generic) return PF_ERR_BAD_SHAPE;          // halo kernel and (round 4) by the generic one when its

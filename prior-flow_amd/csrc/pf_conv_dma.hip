@@ -31,6 +31,12 @@
 // read was consumed (cdna_hip_programming.md "Read a staged buffer one phase AFTER the wait that retires it").
 // Per accumulator the MFMA order over (chunk, tap, ks, pass) is pf_conv_halo_kernel's and the operand bits are the ones it
 // would have made from fp32: results are bit-identical to the fp32-staged kernels (tests/test_hip_kernels.py).
+//
+// F16 (PF_PREC_F16, the update blocks of mixed_precision): the operands are f16 maps -- a 128-byte row holds 64 fp16 channels
+// instead of one 32-channel twin -- and the weights fp16 [Cout_pad][taps][Cin_pad64].  LDS images, swizzle, ring, barriers and
+// the counted vmcnt schedule are the same; a K-step covers 64 channels, the four pieces a lane reads per operand row are four
+// K-groups of 16 instead of hi / lo halves, and a step issues 4 v_mfma_f32_32x32x16_f16 per accumulator instead of 6 bf16
+// MFMAs: the same DMA pieces per step, half the steps per input channel.
 #include <stdlib.h>
 #include "pf_conv_priv.h"
 
@@ -57,7 +63,9 @@ __device__ __forceinline__ void wg_barrier() {
 struct DmaItem { int grp, tile, ntile; };
 
 
-template <int NT, int KH, int KW, int WN>
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+template <int NT, int KH, int KW, int WN, bool F16>
 __global__ void __launch_bounds__(512, 2)
 pf_conv_dma_kernel(const ConvGroups groups, const ConvGeom g) {
     static_assert(WN == 1 || WN == 2, "");
@@ -69,6 +77,7 @@ pf_conv_dma_kernel(const ConvGroups groups, const ConvGeom g) {
     constexpr int WP = BN / 32;                             // weight DMA pieces per loader wave and K-step
     constexpr int SLOT_BYTES = BN * 128;
     constexpr int HSTEPS = TAPS - 3;                        // halo(c+1) is issued at taps 0 .. HSTEPS-1 of chunk c
+    constexpr int CSH = F16 ? 6 : 5;                        // log2(channels per 128-byte operand row)
     extern __shared__ __attribute__((aligned(128))) char smem[];
     constexpr int RING = 2 * HALO_BYTES;                    // byte offset of the weight ring
 
@@ -152,9 +161,9 @@ pf_conv_dma_kernel(const ConvGroups groups, const ConvGeom g) {
             const long rs0 = (long)dd.lds0 * 128, rs1 = (long)dd.lds1 * 128;
             int x0, y0; long pix0;
             tile_origin(it, x0, y0, pix0);
-            seg0 = reinterpret_cast<const char*>(in0s) + (long)(off0 >> 5) * 128;
-            seg1 = reinterpret_cast<const char*>(in1s) + (long)(off1 >> 5) * 128;
-            c0s = c1 > 0 ? c0 >> 5 : nchunks;                     // chunks of segment 0 (the whole K when there is one segment)
+            seg0 = reinterpret_cast<const char*>(in0s) + (long)(off0 >> CSH) * 128;
+            seg1 = reinterpret_cast<const char*>(in1s) + (long)(off1 >> CSH) * 128;
+            c0s = c1 > 0 ? c0 >> CSH : nchunks;                   // chunks of segment 0 (the whole K when there is one segment)
             const long z0 = reinterpret_cast<const char*>(zeros) - seg0, z1 = reinterpret_cast<const char*>(zeros) - seg1;
             static_for<0, HP>([&](auto J) __attribute__((always_inline)) {
                 constexpr int j = decltype(J)::value;
@@ -275,7 +284,8 @@ pf_conv_dma_kernel(const ConvGroups groups, const ConvGeom g) {
     const unsigned arow0 = (unsigned)((2 * wy2) * HW + li);
     const unsigned P0 = 2u * lh;
     const unsigned b_off = (unsigned)(32 * NT * wn + li) * 128 + ((P0 ^ (((unsigned)(32 * NT * wn + li) >> 1) & 7u)) << 4);
-    // fragments, double buffered in registers: [set][...][piece]; pieces 0,1 = hi K-halves, 2,3 = lo K-halves
+    // fragments, double buffered in registers: [set][...][piece]; pieces 0,1 = hi K-halves, 2,3 = lo K-halves (F16: pieces
+    // 0..3 = the K-groups {0-7|16-23}, {8-15|24-31}, {32-39|48-55}, {40-47|56-63} of the 64-channel row, lane half 0|1)
     bf16x8 fa[2][2][4], fb[2][NT][4];
 #ifdef PF_DMA_ABL_NO_READS
     for (int i = 0; i < 2; ++i)
@@ -307,7 +317,7 @@ pf_conv_dma_kernel(const ConvGroups groups, const ConvGeom g) {
     };
     set_a_base();
     constexpr int NP = 8 + 4 * NT;                          // fragment reads per step
-    constexpr int NM = 12 * NT;                             // MFMAs per step
+    constexpr int NM = (F16 ? 8 : 12) * NT;                 // MFMAs per step
     constexpr int FETCH_GAPS = NM - 2;
     auto fetch_piece = [&](auto SET, auto P, unsigned halo_off, auto TAP, unsigned slot_off) __attribute__((always_inline)) {
         constexpr int set = decltype(SET)::value, p = decltype(P)::value, tp = decltype(TAP)::value;
@@ -352,10 +362,15 @@ pf_conv_dma_kernel(const ConvGroups groups, const ConvGeom g) {
             constexpr int i = decltype(I)::value;
             constexpr int idx = i % (2 * NT), m = idx / NT, t = idx % NT, j = i / (2 * NT), ks = j / 3, pass = j % 3;
 #ifdef PF_DMA_ABL_NO_MFMA
-            if constexpr (pass == 0)                      // keep the fragment reads alive, no matrix work
+            if constexpr (F16)
+                asm volatile("" :: "v"(fa[cur][m][j]), "v"(fb[cur][t][j]));
+            else if constexpr (pass == 0)                 // keep the fragment reads alive, no matrix work
                 asm volatile("" :: "v"(fa[cur][m][ks]), "v"(fa[cur][m][2 + ks]), "v"(fb[cur][t][ks]), "v"(fb[cur][t][2 + ks]));
 #else
-            if constexpr (pass == 0)
+            if constexpr (F16)                            // K-group j of the step's 64 channels
+                acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[cur][m][j]),
+                                                                  __builtin_bit_cast(f16x8, fb[cur][t][j]), acc[m][t], 0, 0, 0);
+            else if constexpr (pass == 0)
                 acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cur][m][2 + ks], fb[cur][t][ks], acc[m][t], 0, 0, 0);
             else if constexpr (pass == 1)
                 acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cur][m][ks], fb[cur][t][2 + ks], acc[m][t], 0, 0, 0);
@@ -440,8 +455,8 @@ pf_conv_dma_kernel(const ConvGroups groups, const ConvGeom g) {
 #endif
         (void)d; (void)p0; (void)plim;
 #else
-        if (ragged) tile_epilogue_pair<NT, true>(d, acc, n0 + 32 * NT * wn, li, p0, plim);
-        else tile_epilogue_pair<NT, false>(d, acc, n0 + 32 * NT * wn, li, p0, plim);
+        if (ragged) tile_epilogue_pair<NT, true, F16>(d, acc, n0 + 32 * NT * wn, li, p0, plim);
+        else tile_epilogue_pair<NT, false, F16>(d, acc, n0 + 32 * NT * wn, li, p0, plim);
 #endif
         have = next_item(jm, it);
         // The fragments of the next item's first step were fetched during this item's last step, but keeping them (64 VGPRs)
@@ -455,7 +470,7 @@ pf_conv_dma_kernel(const ConvGroups groups, const ConvGeom g) {
     }
 }
 
-template <int NT, int KH, int KW, int WN>
+template <int NT, int KH, int KW, int WN, bool F16>
 int launch_conv_dma_t(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout, hipStream_t stream) {
     constexpr int BN = 32 * NT * WN, TH = 8 / WN;
     constexpr int HALO_ROWS = ((TH + KH - 1) * (32 + KW - 1) + 31) / 32 * 32;
@@ -489,27 +504,29 @@ int launch_conv_dma_t(const ConvGroups& grp, int ngroups, const ConvGeom& g, int
     if (cap > 0 && cap < 8 && items > cap) cap = 8;
     const dim3 grid((unsigned)((cap > 0 && items > cap) ? cap : items));
     if (!attr_set[dev]) {
-        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&pf_conv_dma_kernel<NT, KH, KW, WN>),
+        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&pf_conv_dma_kernel<NT, KH, KW, WN, F16>),
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (attr != hipSuccess) return (int)attr;
         attr_set[dev] = true;
     }
-    hipLaunchKernelGGL((pf_conv_dma_kernel<NT, KH, KW, WN>), grid, dim3(512), lds, stream, grp, gg);
+    hipLaunchKernelGGL((pf_conv_dma_kernel<NT, KH, KW, WN, F16>), grid, dim3(512), lds, stream, grp, gg);
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
 // One translation unit per kernel shape (PF_DMA_PART = 0..6, compiled in parallel by __graft_entry__.build_hip: an unrolled
-// K-step body takes about a minute per instantiation) plus the dispatcher (PF_DMA_PART = 7).
+// K-step body takes about a minute per instantiation) plus the dispatcher (PF_DMA_PART = 7).  A unit holds both operand forms
+// of its shape (split twins and f16 maps).
 //   part: 0 <2,3,3,1>  1 <2,3,3,2>  2 <2,1,5,2>  3 <2,5,1,2>  4 <1,3,3,2>  5 <1,1,5,2>  6 <1,5,1,2>  8 <2,1,5,1>  9 <2,5,1,1>   (<NT, KH, KW, WN>)
 #ifndef PF_DMA_PART
 #error "compile pf_conv_dma.hip with -DPF_DMA_PART=0..7"
 #endif
 #define PF_DMA_DEFINE_PART(N, NT, KH, KW, WN)                                                                              \
     int pf_conv_dma_part##N##_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout,   \
-                                     hipStream_t stream) {                                                                  \
-        return launch_conv_dma_t<NT, KH, KW, WN>(grp, ngroups, g, max_cout, stream);                                        \
+                                     bool f16, hipStream_t stream) {                                                        \
+        return f16 ? launch_conv_dma_t<NT, KH, KW, WN, true>(grp, ngroups, g, max_cout, stream)                             \
+                   : launch_conv_dma_t<NT, KH, KW, WN, false>(grp, ngroups, g, max_cout, stream);                           \
     }
 #if PF_DMA_PART == 0
 PF_DMA_DEFINE_PART(0, 2, 3, 3, 1)
@@ -530,7 +547,7 @@ PF_DMA_DEFINE_PART(8, 2, 1, 5, 1)
 #elif PF_DMA_PART == 9
 PF_DMA_DEFINE_PART(9, 2, 5, 1, 1)
 #else
-#define PF_DMA_DECLARE_PART(N) int pf_conv_dma_part##N##_launch(const pfconv::ConvGroups&, int, const pfconv::ConvGeom&, int, hipStream_t);
+#define PF_DMA_DECLARE_PART(N) int pf_conv_dma_part##N##_launch(const pfconv::ConvGroups&, int, const pfconv::ConvGeom&, int, bool, hipStream_t);
 PF_DMA_DECLARE_PART(0) PF_DMA_DECLARE_PART(1) PF_DMA_DECLARE_PART(2) PF_DMA_DECLARE_PART(3)
 PF_DMA_DECLARE_PART(4) PF_DMA_DECLARE_PART(5) PF_DMA_DECLARE_PART(6) PF_DMA_DECLARE_PART(8) PF_DMA_DECLARE_PART(9)
 
@@ -539,20 +556,21 @@ int pf_conv_dma_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv:
     for (int i = 0; i < ngroups; ++i)
         if (!grp.d[i].zeros || grp.d[i].zeros_bytes < 128 * (grp.d[i].lds0 > grp.d[i].lds1 ? grp.d[i].lds0 : grp.d[i].lds1)) return PF_ERR_BAD_ARG;
     const bool k33 = g.kh == 3 && g.kw == 3, k15 = g.kh == 1 && g.kw == 5, k51 = g.kh == 5 && g.kw == 1;
+    const bool f16 = grp.d[0].precision == PF_PREC_F16;
     if (roles == 2) {           // 256 px x 64 channels per workgroup: half the weight bytes staged per output, twice the halo
-        if (k33) return pf_conv_dma_part0_launch(grp, ngroups, g, max_cout, stream);
-        if (k15) return pf_conv_dma_part8_launch(grp, ngroups, g, max_cout, stream);
-        if (k51) return pf_conv_dma_part9_launch(grp, ngroups, g, max_cout, stream);
+        if (k33) return pf_conv_dma_part0_launch(grp, ngroups, g, max_cout, f16, stream);
+        if (k15) return pf_conv_dma_part8_launch(grp, ngroups, g, max_cout, f16, stream);
+        if (k51) return pf_conv_dma_part9_launch(grp, ngroups, g, max_cout, f16, stream);
         return PF_ERR_BAD_SHAPE;
     }
     if (nt == 2) {
-        if (k33) return pf_conv_dma_part1_launch(grp, ngroups, g, max_cout, stream);
-        if (k15) return pf_conv_dma_part2_launch(grp, ngroups, g, max_cout, stream);
-        if (k51) return pf_conv_dma_part3_launch(grp, ngroups, g, max_cout, stream);
+        if (k33) return pf_conv_dma_part1_launch(grp, ngroups, g, max_cout, f16, stream);
+        if (k15) return pf_conv_dma_part2_launch(grp, ngroups, g, max_cout, f16, stream);
+        if (k51) return pf_conv_dma_part3_launch(grp, ngroups, g, max_cout, f16, stream);
     } else {
-        if (k33) return pf_conv_dma_part4_launch(grp, ngroups, g, max_cout, stream);
-        if (k15) return pf_conv_dma_part5_launch(grp, ngroups, g, max_cout, stream);
-        if (k51) return pf_conv_dma_part6_launch(grp, ngroups, g, max_cout, stream);
+        if (k33) return pf_conv_dma_part4_launch(grp, ngroups, g, max_cout, f16, stream);
+        if (k15) return pf_conv_dma_part5_launch(grp, ngroups, g, max_cout, f16, stream);
+        if (k51) return pf_conv_dma_part6_launch(grp, ngroups, g, max_cout, f16, stream);
     }
     return PF_ERR_BAD_SHAPE;
 }

@@ -102,13 +102,31 @@ __device__ __forceinline__ void pf_store_split_pairs(char* sp, long rs, const V&
     });
 }
 
+// The same for an f16 map (PF_PREC_F16 operand; `sp`: this lane's EVEN channel at row p0 of the map): one fp16 pair per row.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+template <bool CHECK, class V>
+__device__ __forceinline__ void pf_store_f16_pairs(char* sp, long rs, const V& v, bool odd, long p0, long plimit) {
+    static_for<0, 8>([&](auto K) __attribute__((always_inline)) {
+        constexpr int k = decltype(K)::value;
+        const float send = odd ? v[k] : v[k + 8];
+        const float recv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), 0xB1, 0xf, 0xf, true));   // lane ^ 1
+        const f32x2 ab = {odd ? recv : v[k], odd ? v[k + 8] : recv};
+        constexpr int ro = (k & 3) + 8 * (k >> 2);
+        const long row = ro + (odd ? 16 : 0);
+        const f16x2 h = __builtin_convertvector(ab, f16x2);
+        if (!CHECK || p0 + row < plimit) *reinterpret_cast<f16x2*>(sp + row * rs) = h;
+    });
+}
+
 // Fused epilogue of a wave's NT 32x32 accumulators.  acc[t][r] is output channel jb + 32 t + li
 // of pixel p0 + (r&3) + 8 (r>>2)  (p0 already holds the lane's +4*(lane>>5) row offset).
 // The kind is tested once per tile, a lane keeps one base pointer per array and adds row * ld offsets, the channel-half
 // decisions of the split epilogues are wave-uniform (jb is scalar), and the GRU operands of a tile are gathered before
 // anything is stored.  Every output exists in up to two forms: fp32 rows (`out` / `aux_out`, may be NULL when the twin is
-// given) and the bf16 hi|lo split twin (`out_split` / `aux_split`) the DMA-fed convolutions consume.
-template <int NT, bool CHECK, bool FAST>
+// given) and the bf16 hi|lo split twin (`out_split` / `aux_split`) the DMA-fed convolutions consume -- or, with F16OUT
+// (compile time: the kernels that never write f16 maps keep exactly their code), the f16 map (fp16 round to nearest even, 64
+// channels per 128-byte unit) of the PF_PREC_F16 update blocks.
+template <int NT, bool CHECK, bool FAST, bool F16OUT = false>
 __device__ __forceinline__ void tile_epilogue_t(const pf_conv_desc& d, const f32x16 (&acc)[NT], int jb, int li,
                                                 long p0, long plimit) {
     const int epi = d.epilogue;
@@ -122,7 +140,15 @@ __device__ __forceinline__ void tile_epilogue_t(const pf_conv_desc& d, const f32
             for (int r = 0; r < 16; ++r)
                 if (live(r)) o[(long)roff(r) * ld] = v[r];      // (nt stores here: no effect, profiles/r5_ab_epilogue_nt.txt)
         }
-        if (sbase != nullptr) {
+        if constexpr (F16OUT) {
+            if (sbase != nullptr) {
+                char* sp = reinterpret_cast<char*>(sbase) + ((p0 * lds + (col >> 6)) * 128 + 2 * (col & 63));
+                const long rs = (long)lds * 128;
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (live(r)) *reinterpret_cast<_Float16*>(sp + roff(r) * rs) = (_Float16)v[r];
+            }
+        } else if (sbase != nullptr) {
             char* sp = reinterpret_cast<char*>(sbase) + ((p0 * lds + (col >> 5)) * 128 + 2 * (col & 31));
             const long rs = (long)lds * 128;
 #pragma unroll
@@ -212,7 +238,7 @@ __device__ __forceinline__ void tile_epilogue_t(const pf_conv_desc& d, const f32
 // form above alternates loads and stores, and since `out` may alias `h` as far as the compiler knows, each tile's loads
 // wait behind the previous tile's stores: up to four dependent global round trips (s_memtime stamps of
 // pf_conv_dma_kernel: 7 300 cycles from the end of the K loop to the last store retired, a tenth of a GRU launch).
-template <int NT, bool CHECK, bool FAST>
+template <int NT, bool CHECK, bool FAST, bool F16OUT = false>
 __device__ __forceinline__ void tile_epilogue_pair_t(const pf_conv_desc& d, const f32x16 (&acc)[2][NT], int jb, int li,
                                                      const long (&p0)[2], const long (&plimit)[2]) {
     const int epi = d.epilogue;
@@ -258,7 +284,16 @@ __device__ __forceinline__ void tile_epilogue_pair_t(const pf_conv_desc& d, cons
                     if (!CHECK || pm + roff(r) < pl) o[(long)roff(r) * ld] = v[r];
                 });
             }
-            if (sbase != nullptr) {
+            if constexpr (F16OUT) {
+                if (sbase != nullptr) {
+                    char* sp = reinterpret_cast<char*>(sbase) + ((pm * lds + (col >> 6)) * 128 + 2 * (col & 63));
+                    const long rs = (long)lds * 128;
+                    static_for<0, 16>([&](auto R) __attribute__((always_inline)) {
+                        constexpr int r = decltype(R)::value;
+                        if (!CHECK || pm + roff(r) < pl) *reinterpret_cast<_Float16*>(sp + roff(r) * rs) = (_Float16)v[r];
+                    });
+                }
+            } else if (sbase != nullptr) {
                 char* sp = reinterpret_cast<char*>(sbase) + ((pm * lds + (col >> 5)) * 128 + 2 * (col & 31));
                 const long rs = (long)lds * 128;
                 static_for<0, 16>([&](auto R) __attribute__((always_inline)) {
@@ -320,19 +355,21 @@ __device__ __forceinline__ void tile_epilogue_pair_t(const pf_conv_desc& d, cons
     });
 }
 
-template <int NT, bool CHECK>
+template <int NT, bool CHECK, bool F16OUT = false>
 __device__ __forceinline__ void tile_epilogue_pair(const pf_conv_desc& d, const f32x16 (&acc)[2][NT], int jb, int li,
                                                    const long (&p0)[2], const long (&plimit)[2]) {
     const bool gated = d.epilogue == PF_EPI_GRU_ZR || d.epilogue == PF_EPI_GRU_Q || d.epilogue == PF_EPI_TANH_RELU;
-    if (gated && d.precision == PF_PREC_F32) tile_epilogue_pair_t<NT, CHECK, false>(d, acc, jb, li, p0, plimit);
+    if constexpr (F16OUT) tile_epilogue_pair_t<NT, CHECK, true, true>(d, acc, jb, li, p0, plimit);
+    else if (gated && d.precision == PF_PREC_F32) tile_epilogue_pair_t<NT, CHECK, false>(d, acc, jb, li, p0, plimit);
     else tile_epilogue_pair_t<NT, CHECK, true>(d, acc, jb, li, p0, plimit);
 }
 
-template <int NT, bool CHECK>
+template <int NT, bool CHECK, bool F16OUT = false>
 __device__ __forceinline__ void tile_epilogue(const pf_conv_desc& d, const f32x16 (&acc)[NT], int jb, int li,
                                               long p0, long plimit) {
     const bool gated = d.epilogue == PF_EPI_GRU_ZR || d.epilogue == PF_EPI_GRU_Q || d.epilogue == PF_EPI_TANH_RELU;
-    if (gated && d.precision == PF_PREC_F32) tile_epilogue_t<NT, CHECK, false>(d, acc, jb, li, p0, plimit);
+    if constexpr (F16OUT) tile_epilogue_t<NT, CHECK, true, true>(d, acc, jb, li, p0, plimit);
+    else if (gated && d.precision == PF_PREC_F32) tile_epilogue_t<NT, CHECK, false>(d, acc, jb, li, p0, plimit);
     else tile_epilogue_t<NT, CHECK, true>(d, acc, jb, li, p0, plimit);
 }
 
@@ -355,6 +392,7 @@ bool pf_enc_conv64_applies(const pfconv::ConvGroups& grp, int ngroups, const pfc
 int pf_enc_conv64_stats_blocks(const pfconv::ConvGeom& g);
 int pf_enc_conv64_launch(const pfconv::ConvGroups& grp, const pfconv::ConvGeom& g, hipStream_t stream);
 
-// pf_conv_dma.hip: launcher of the all-DMA kernel.  `roles` as in pf_conv2d_roles (1: 128-px tile, 2: 256 px x 64 channels).
+// pf_conv_dma.hip: launcher of the all-DMA kernel.  `roles` as in pf_conv2d_roles (1: 128-px tile, 2: 256 px x 64 channels);
+// the operand form (split twins or f16 maps) follows grp.d[0].precision.
 int pf_conv_dma_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, int nt, int roles,
                        hipStream_t stream);

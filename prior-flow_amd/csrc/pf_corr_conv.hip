@@ -33,7 +33,7 @@ constexpr int CC_COUT = 256;
 constexpr int CC_LDS_A = 2 * CC_PX * 128;       // bytes: two 32-channel chunks of the combined tile
 constexpr int CC_LDS = CC_LDS_A + CC_PX * 8 * 4;
 
-struct CombGroups { pf_combine_conv_desc d[2]; };
+struct CombGroups { pf_combine_conv_desc d[2]; int f16; };     // f16: out_split is an f16 map (PF_PREC_F16 operand)
 
 template <int I, int N, class F>
 __device__ __forceinline__ void cc_for(F&& f) {
@@ -213,8 +213,13 @@ pf_combine_conv_kernel(const CombGroups groups, const int B, const int H, const 
                 float v[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] = fmaxf(acc[m][t][r] + bias, 0.f);
-                char* sp = pf_split_ptr(d.out_split, prow, d.lds_out, (d.off_out + ch) & ~1);
-                pfconv::pf_store_split_pairs<true>(sp, (long)d.lds_out * 128, v, (ch & 1) != 0, prow, rows);
+                if (groups.f16) {
+                    char* sp = pf_f16_ptr(d.out_split, prow, d.lds_out, (d.off_out + ch) & ~1);
+                    pfconv::pf_store_f16_pairs<true>(sp, (long)d.lds_out * 128, v, (ch & 1) != 0, prow, rows);
+                } else {
+                    char* sp = pf_split_ptr(d.out_split, prow, d.lds_out, (d.off_out + ch) & ~1);
+                    pfconv::pf_store_split_pairs<true>(sp, (long)d.lds_out * 128, v, (ch & 1) != 0, prow, rows);
+                }
             }
         }
     }
@@ -222,7 +227,7 @@ pf_combine_conv_kernel(const CombGroups groups, const int B, const int H, const 
 
 }  // namespace
 
-extern "C" int pf_dccl_combine_conv1x1(const pf_combine_conv_desc* descs, int ngroups, int B, int H8, int W8, void* stream) {
+static int combine_conv_impl(const pf_combine_conv_desc* descs, int ngroups, int B, int H8, int W8, int f16, void* stream) {
     if (!descs || ngroups < 1 || ngroups > 2) return PF_ERR_BAD_ARG;
     if (B <= 0 || H8 <= 1 || W8 <= 1) return PF_ERR_BAD_SHAPE;
     CombGroups g;
@@ -230,10 +235,11 @@ extern "C" int pf_dccl_combine_conv1x1(const pf_combine_conv_desc* descs, int ng
         const pf_combine_conv_desc& d = descs[i];
         if (!d.own || !d.raw || !d.g_back || !d.weight || !d.bias || (!d.out && !d.out_split)) return PF_ERR_BAD_ARG;
         if (d.cout != CC_COUT || d.ld < CC_CIN || (d.ld & 3) || d.off_out < 0 || (d.out && d.off_out + d.cout > d.ld_out)) return PF_ERR_BAD_SHAPE;
-        if (d.out_split && ((d.off_out & 31) || d.off_out + d.cout > d.lds_out * 32)) return PF_ERR_BAD_SHAPE;
+        if (d.out_split && ((d.off_out & 31) || d.off_out + d.cout > d.lds_out * (f16 ? 64 : 32))) return PF_ERR_BAD_SHAPE;
         g.d[i] = d;
     }
     if (ngroups == 1) g.d[1] = g.d[0];
+    g.f16 = f16;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&pf_combine_conv_kernel),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, CC_LDS);
     if (attr != hipSuccess) return (int)attr;
@@ -241,4 +247,12 @@ extern "C" int pf_dccl_combine_conv1x1(const pf_combine_conv_desc* descs, int ng
     dim3 grid((unsigned)((rows + CC_PX - 1) / CC_PX), (unsigned)ngroups);
     hipLaunchKernelGGL(pf_combine_conv_kernel, grid, dim3(256), CC_LDS, (hipStream_t)stream, g, B, H8, W8);
     return (int)hipGetLastError();
+}
+
+extern "C" int pf_dccl_combine_conv1x1(const pf_combine_conv_desc* descs, int ngroups, int B, int H8, int W8, void* stream) {
+    return combine_conv_impl(descs, ngroups, B, H8, W8, 0, stream);
+}
+
+extern "C" int pf_dccl_combine_conv1x1_f16(const pf_combine_conv_desc* descs, int ngroups, int B, int H8, int W8, void* stream) {
+    return combine_conv_impl(descs, ngroups, B, H8, W8, 1, stream);
 }

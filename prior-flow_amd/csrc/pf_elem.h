@@ -36,6 +36,24 @@ PF_HD void pf_split_put(void* base, long row, int lds, int ch, float x) {
     o[0] = hi;
     o[32] = pf_bf16_rne(x - pf_bf16_to_f32(hi));
 }
+// fp32 -> IEEE fp16 bits, round to nearest even, overflow to Inf, gradual underflow (v_cvt_f16_f32's result for every input;
+// written out so that the host build of this file needs no compiler fp16 type)
+PF_HD unsigned short pf_f16_rne(float f) {
+    union { float f; unsigned u; } v; v.f = f;
+    const unsigned sign = (v.u >> 16) & 0x8000u, a = v.u & 0x7fffffffu;
+    if (a >= 0x7f800000u) return (unsigned short)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u));   // NaN / Inf
+    if (a >= 0x477ff000u) return (unsigned short)(sign | 0x7c00u);                                  // >= 65520: Inf
+    if (a >= 0x38800000u)                                                                           // normal (>= 2^-14)
+        return (unsigned short)(sign | ((a + 0x0fffu + ((a >> 13) & 1u) - 0x38000000u) >> 13));
+    const int shift = 126 - (int)(a >> 23);                     // subnormal: units of 2^-24
+    if (shift > 24) return (unsigned short)sign;
+    const unsigned m = (a & 0x7fffffu) | 0x800000u, q = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    return (unsigned short)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
+}
+// element (row, ch) of an f16 map [rows][lds units]{fp16[64]} (include/priorflow_hip.h, PF_PREC_F16)
+PF_HD void pf_f16_put(void* base, long row, int lds, int ch, float x) {
+    reinterpret_cast<unsigned short*>(base)[(row * lds + (ch >> 6)) * 64 + (ch & 63)] = pf_f16_rne(x);
+}
 
 // Python-style float remainder for b > 0 (`xgrid % W`, core/utils/utils.py:83; ATen: fmod, then +b when
 // the signs differ), bit for bit, without the device's (long, loop-based) fmodf:
@@ -890,6 +908,7 @@ struct PfDirectConvArgs {
     int B, H, W, KH, KW, relu;      // H, W: OUTPUT map
     int stride, nchw, Hin, Win;     // input map = stride x output; nchw: input is [B,Cin,Hin,Win] planes
     void* out_split; int lds_out;   // optional split twin of `out` (same channel offset); `out` may then be null
+    int out_f16;                    // out_split is an f16 map (PF_PREC_F16 operand) instead of a split twin
 };
 PF_HD void pf_direct_conv_elem(long idx, const PfDirectConvArgs& a) {  // idx over B*N*Cout
     const long N = (long)a.H * a.W, Nin = (long)a.Hin * a.Win;
@@ -916,7 +935,10 @@ PF_HD void pf_direct_conv_elem(long idx, const PfDirectConvArgs& a) {  // idx ov
     acc = acc + a.bias[co];
     if (a.relu) acc = fmaxf(acc, 0.f);
     if (a.out) a.out[row * a.ld_out + a.c_out_off + co] = acc;
-    if (a.out_split) pf_split_put(a.out_split, row, a.lds_out, a.c_out_off + co, acc);
+    if (a.out_split) {
+        if (a.out_f16) pf_f16_put(a.out_split, row, a.lds_out, a.c_out_off + co, acc);
+        else pf_split_put(a.out_split, row, a.lds_out, a.c_out_off + co, acc);
+    }
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -967,6 +989,19 @@ PF_HD void pf_split_bf16_elem(long idx, const PfSplitArgs& a) {   // idx over ro
         o[i] = hi;
         o[32 + i] = pf_bf16_rne(x - pf_bf16_to_f32(hi));
     }
+}
+
+// fp32 rows -> f16 map (operand format of the PF_PREC_F16 update-block convolutions): out row = lds units of 64 fp16
+// channels, channel c of row r at out[r * lds * 64 + c] = fp16_rne(in[r * ld_in + c]); columns >= C are not written.
+struct PfSplitF16Args { const float* in; unsigned short* out; long rows; int C, ld_in, lds; };
+PF_HD void pf_split_f16_elem(long idx, const PfSplitF16Args& a) {   // idx over rows*C/4
+    const int c4n = a.C / 4;
+    const int c = (int)(idx % c4n) * 4;
+    const long row = idx / c4n;
+    const float* x = a.in + row * a.ld_in + c;
+    const unsigned long long v = (unsigned long long)pf_f16_rne(x[0]) | ((unsigned long long)pf_f16_rne(x[1]) << 16) |
+                                 ((unsigned long long)pf_f16_rne(x[2]) << 32) | ((unsigned long long)pf_f16_rne(x[3]) << 48);
+    *reinterpret_cast<unsigned long long*>(a.out + row * a.lds * 64 + c) = v;          // 4 channels, one 8-byte store
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1302,6 +1337,7 @@ struct PfMotionPrepArgs {
     PfDst xa, xb;                            // GRU input tails: 4 columns (flow_A | flow_B_A) / 2 columns (flow_B)
     void* xa_split; int xa_lds;              // optional split twins of the GRU input buffers (same channel offsets as xa / xb)
     void* xb_split; int xb_lds;
+    int f16;                                 // the two above are f16 maps (PF_PREC_F16 operands) instead of split twins
     float* conf; int conf_ld;                // [B*N][conf_ld]: columns 0..3 flaw_A, 4..7 flaw_B_A
     int B, H, W;
 };

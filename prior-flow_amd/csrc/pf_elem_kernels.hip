@@ -136,14 +136,26 @@ __global__ void __launch_bounds__(256) pf_motion_prep_kernel(const PfMotionPrepA
             d[0] = f.ua; d[1] = f.va; d[2] = f.uba; d[3] = f.vba;
         }
         pf_store_dst2(a.xb, row, f.ub, f.vb);
-        if (a.xa_split) {
-            const float v4[4] = {f.ua, f.va, f.uba, f.vba};
+        if (a.f16) {                 // f16 maps (PF_PREC_F16 update blocks)
+            if (a.xa_split) {
+                const float v4[4] = {f.ua, f.va, f.uba, f.vba};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) pf_split_store(pf_split_ptr(a.xa_split, row, a.xa_lds, a.xa.c_off + i), v4[i]);
-        }
-        if (a.xb_split) {
-            pf_split_store(pf_split_ptr(a.xb_split, row, a.xb_lds, a.xb.c_off), f.ub);
-            pf_split_store(pf_split_ptr(a.xb_split, row, a.xb_lds, a.xb.c_off + 1), f.vb);
+                for (int i = 0; i < 4; ++i) pf_f16_store(pf_f16_ptr(a.xa_split, row, a.xa_lds, a.xa.c_off + i), v4[i]);
+            }
+            if (a.xb_split) {
+                pf_f16_store(pf_f16_ptr(a.xb_split, row, a.xb_lds, a.xb.c_off), f.ub);
+                pf_f16_store(pf_f16_ptr(a.xb_split, row, a.xb_lds, a.xb.c_off + 1), f.vb);
+            }
+        } else {
+            if (a.xa_split) {
+                const float v4[4] = {f.ua, f.va, f.uba, f.vba};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pf_split_store(pf_split_ptr(a.xa_split, row, a.xa_lds, a.xa.c_off + i), v4[i]);
+            }
+            if (a.xb_split) {
+                pf_split_store(pf_split_ptr(a.xb_split, row, a.xb_lds, a.xb.c_off), f.ub);
+                pf_split_store(pf_split_ptr(a.xb_split, row, a.xb_lds, a.xb.c_off + 1), f.vb);
+            }
         }
         // sample points of the two warps: coords1_A (:173) and coords0 + flow_B_A (:180)
         flows[tid][0] = a.c1a[(b * 2 + 0) * N + n]; flows[tid][1] = a.c1a[(b * 2 + 1) * N + n];
@@ -211,6 +223,7 @@ struct PfSmallConvArgs {
     const float* w; const float* bias;                        // [KH*KW*Cin][Cout]
     float* out; int ld_out, c_out_off, Cout;                  // channel-last
     void* out_split; int lds_out;                             // optional split twin of `out` (pf_stem7x7c2_valu only)
+    int out_f16;                                              // out_split is an f16 map instead (PF_PREC_F16 operand)
     int B, H, W;                                              // INPUT spatial size
     int KH, KW, stride, relu;
     int Ho, Wo;                                               // output size (H/stride, W/stride)
@@ -417,7 +430,8 @@ __global__ void __launch_bounds__(128) pf_stem7x7c2_valu(const PfSmallConvMulti 
 #pragma unroll
             for (int i = 0; i < CPW; i += 8) {
                 const float v8[8] = {acc[i], acc[i + 1], acc[i + 2], acc[i + 3], acc[i + 4], acc[i + 5], acc[i + 6], acc[i + 7]};
-                pf_split_store_n<8>(pf_split_ptr(a.out_split, row, a.lds_out, a.c_out_off + co0 + i), v8);
+                if (a.out_f16) pf_f16_store_n<8>(pf_f16_ptr(a.out_split, row, a.lds_out, a.c_out_off + co0 + i), v8);
+                else pf_split_store_n<8>(pf_split_ptr(a.out_split, row, a.lds_out, a.c_out_off + co0 + i), v8);
             }
         }
     }
@@ -1242,7 +1256,7 @@ static int pf_direct_conv_dispatch_n(const PfDirectConvArgs* ds, int n, long tot
             a.w = e.w; a.bias = e.bias; a.out = e.out; a.ld_out = e.ld_out; a.c_out_off = e.c_out_off; a.Cout = e.Cout;
             a.B = e.B; a.H = e.Hin; a.W = e.Win; a.KH = e.KH; a.KW = e.KW; a.stride = e.stride; a.relu = e.relu;
             a.Ho = e.H; a.Wo = e.W;
-            a.out_split = e.out_split; a.lds_out = e.lds_out;
+            a.out_split = e.out_split; a.lds_out = e.lds_out; a.out_f16 = e.out_f16;
         }
         for (int i = n; i < 4; ++i) m.p[i] = m.p[0];
         bool valu = true;
@@ -1258,6 +1272,7 @@ static int pf_direct_conv_dispatch_n(const PfDirectConvArgs* ds, int n, long tot
                     PfFlowStemProblem& q = fm.p[i];
                     q.in = a.in; q.ld_in = a.ld_in; q.c_in_off = a.c_in_off; q.w = a.w; q.bias = a.bias;
                     q.out = a.out; q.ld_out = a.ld_out; q.c_out_off = a.c_out_off; q.out_split = a.out_split; q.lds_out = a.lds_out;
+                    q.out_f16 = a.out_f16;
                     q.relu = a.relu;
                 }
                 fm.B = m.p[0].B; fm.H = m.p[0].H; fm.W = m.p[0].W;
@@ -1315,6 +1330,7 @@ struct PfConfStemArgs {
     const float* w2; const float* b2;       // [9*32][16], [16]
     float* out; int ld_out, off_out;
     void* out_split; int lds_out;
+    int f16;                                // out_split is an f16 map (PF_PREC_F16 operand) instead of a split twin
     int B, H, W;
 };
 __global__ void __launch_bounds__(256) pf_conf_stem_kernel(const PfConfStemArgs a) {
@@ -1391,21 +1407,22 @@ __global__ void __launch_bounds__(256) pf_conf_stem_kernel(const PfConfStemArgs 
         if (a.out != nullptr) *reinterpret_cast<float4*>(a.out + row * a.ld_out + a.off_out + 4 * cg) = r;
         if (a.out_split != nullptr) {
             const float v4[4] = {r.x, r.y, r.z, r.w};
-            pf_split_store_n<4>(pf_split_ptr(a.out_split, row, a.lds_out, a.off_out + 4 * cg), v4);
+            if (a.f16) pf_f16_store_n<4>(pf_f16_ptr(a.out_split, row, a.lds_out, a.off_out + 4 * cg), v4);
+            else pf_split_store_n<4>(pf_split_ptr(a.out_split, row, a.lds_out, a.off_out + 4 * cg), v4);
         }
     }
 }
 
-extern "C" int pf_conf_stem(const float* in, int ld_in, int off_in, const float* w1, const float* b1,
-                            const float* w2, const float* b2, float* out, int ld_out, int off_out,
-                            void* out_split, int lds_out, int B, int H8, int W8, void* stream) {
+static int conf_stem_impl(const float* in, int ld_in, int off_in, const float* w1, const float* b1,
+                          const float* w2, const float* b2, float* out, int ld_out, int off_out,
+                          void* out_split, int lds_out, int f16, int B, int H8, int W8, void* stream) {
     if (!in || !w1 || !b1 || !w2 || !b2 || (!out && !out_split)) return PF_ERR_BAD_ARG;
     if (B <= 0 || H8 <= 0 || W8 <= 0) return PF_ERR_BAD_SHAPE;
     if (off_in < 0 || off_in + CS_CIN > ld_in || off_out < 0 || (out && off_out + CS_OUT > ld_out)) return PF_ERR_BAD_ARG;
-    if (out_split && off_out + CS_OUT > lds_out * 32) return PF_ERR_BAD_ARG;
+    if (out_split && off_out + CS_OUT > lds_out * (f16 ? 64 : 32)) return PF_ERR_BAD_ARG;
     if ((ld_in | off_in | off_out) & 3 || (out && (ld_out & 3))) return PF_ERR_BAD_SHAPE;          // 16-byte rows
     PfConfStemArgs a;
-    a.out_split = out_split; a.lds_out = lds_out;
+    a.out_split = out_split; a.lds_out = lds_out; a.f16 = f16;
     a.in = in; a.ld_in = ld_in; a.off_in = off_in; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
     a.out = out; a.ld_out = ld_out; a.off_out = off_out; a.B = B; a.H = H8; a.W = W8;
     const long tiles = (long)B * ((H8 + CS_TH - 1) / CS_TH) * ((W8 + CS_TW - 1) / CS_TW);
@@ -1413,19 +1430,32 @@ extern "C" int pf_conf_stem(const float* in, int ld_in, int off_in, const float*
     return (int)hipGetLastError();
 }
 
-extern "C" int pf_motion_prep(const float* c1a, const float* c1b, const float* g_w2c, const float* g_c2w,
-                              const float* f1a, const float* f2a, float* flow4_a, float* flow2_b,
-                              float* xa, int xa_ld, int xa_off, float* xb, int xb_ld, int xb_off,
-                              void* xa_split, int xa_lds, void* xb_split, int xb_lds,
-                              float* conf, int conf_ld, int B, int H8, int W8, int C, void* stream) {
+extern "C" int pf_conf_stem(const float* in, int ld_in, int off_in, const float* w1, const float* b1,
+                            const float* w2, const float* b2, float* out, int ld_out, int off_out,
+                            void* out_split, int lds_out, int B, int H8, int W8, void* stream) {
+    return conf_stem_impl(in, ld_in, off_in, w1, b1, w2, b2, out, ld_out, off_out, out_split, lds_out, 0, B, H8, W8, stream);
+}
+
+extern "C" int pf_conf_stem_f16(const float* in, int ld_in, int off_in, const float* w1, const float* b1,
+                                const float* w2, const float* b2, float* out, int ld_out, int off_out,
+                                void* out_f16, int lds_out, int B, int H8, int W8, void* stream) {
+    return conf_stem_impl(in, ld_in, off_in, w1, b1, w2, b2, out, ld_out, off_out, out_f16, lds_out, 1, B, H8, W8, stream);
+}
+
+static int motion_prep_impl(const float* c1a, const float* c1b, const float* g_w2c, const float* g_c2w,
+                            const float* f1a, const float* f2a, float* flow4_a, float* flow2_b,
+                            float* xa, int xa_ld, int xa_off, float* xb, int xb_ld, int xb_off,
+                            void* xa_split, int xa_lds, void* xb_split, int xb_lds, int f16,
+                            float* conf, int conf_ld, int B, int H8, int W8, int C, void* stream) {
     if (!c1a || !c1b || !g_w2c || !g_c2w || !f1a || !f2a || !flow4_a || !flow2_b || !conf) return PF_ERR_BAD_ARG;
     if (B <= 0 || H8 <= 1 || W8 <= 1 || C != 256 || conf_ld < 8) return PF_ERR_BAD_SHAPE;
     if (xa && (xa_off < 0 || xa_off + 4 > xa_ld)) return PF_ERR_BAD_ARG;
     if (xb && (xb_off < 0 || xb_off + 2 > xb_ld)) return PF_ERR_BAD_ARG;
-    if (xa_split && (xa_off < 0 || xa_off + 4 > xa_lds * 32)) return PF_ERR_BAD_ARG;
-    if (xb_split && (xb_off < 0 || xb_off + 2 > xb_lds * 32)) return PF_ERR_BAD_ARG;
+    const int cpu = f16 ? 64 : 32;          // channels per 128-byte unit of a row
+    if (xa_split && (xa_off < 0 || xa_off + 4 > xa_lds * cpu)) return PF_ERR_BAD_ARG;
+    if (xb_split && (xb_off < 0 || xb_off + 2 > xb_lds * cpu)) return PF_ERR_BAD_ARG;
     PfMotionPrepArgs a;
-    a.xa_split = xa_split; a.xa_lds = xa_lds; a.xb_split = xb_split; a.xb_lds = xb_lds;
+    a.xa_split = xa_split; a.xa_lds = xa_lds; a.xb_split = xb_split; a.xb_lds = xb_lds; a.f16 = f16;
     a.c1a = c1a; a.c1b = c1b; a.g_w2c = g_w2c; a.g_c2w = g_c2w; a.f1 = f1a; a.f2 = f2a;
     a.flow4_a = flow4_a; a.flow2_b = flow2_b;
     a.xa = pf_dst(xa, xa_ld, xa_off); a.xb = pf_dst(xb, xb_ld, xb_off);
@@ -1434,6 +1464,24 @@ extern "C" int pf_motion_prep(const float* c1a, const float* c1b, const float* g
     hipLaunchKernelGGL(pf_motion_prep_kernel, dim3((unsigned)((rows + MP_PIX - 1) / MP_PIX)), dim3(256), 0,
                        (hipStream_t)stream, a, rows);
     return (int)hipGetLastError();
+}
+
+extern "C" int pf_motion_prep(const float* c1a, const float* c1b, const float* g_w2c, const float* g_c2w,
+                              const float* f1a, const float* f2a, float* flow4_a, float* flow2_b,
+                              float* xa, int xa_ld, int xa_off, float* xb, int xb_ld, int xb_off,
+                              void* xa_split, int xa_lds, void* xb_split, int xb_lds,
+                              float* conf, int conf_ld, int B, int H8, int W8, int C, void* stream) {
+    return motion_prep_impl(c1a, c1b, g_w2c, g_c2w, f1a, f2a, flow4_a, flow2_b, xa, xa_ld, xa_off, xb, xb_ld, xb_off,
+                            xa_split, xa_lds, xb_split, xb_lds, 0, conf, conf_ld, B, H8, W8, C, stream);
+}
+
+extern "C" int pf_motion_prep_f16(const float* c1a, const float* c1b, const float* g_w2c, const float* g_c2w,
+                                  const float* f1a, const float* f2a, float* flow4_a, float* flow2_b,
+                                  float* xa, int xa_ld, int xa_off, float* xb, int xb_ld, int xb_off,
+                                  void* xa_f16, int xa_lds, void* xb_f16, int xb_lds,
+                                  float* conf, int conf_ld, int B, int H8, int W8, int C, void* stream) {
+    return motion_prep_impl(c1a, c1b, g_w2c, g_c2w, f1a, f2a, flow4_a, flow2_b, xa, xa_ld, xa_off, xb, xb_ld, xb_off,
+                            xa_f16, xa_lds, xb_f16, xb_lds, 1, conf, conf_ld, B, H8, W8, C, stream);
 }
 
 extern "C" const char* pf_version(void) {

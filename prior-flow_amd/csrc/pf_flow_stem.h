@@ -6,6 +6,7 @@ struct PfFlowStemProblem {
     const float* w; const float* bias;             // [7*7*2][128] fp32 (k = (ky*7 + kx)*2 + c), [128]
     float* out; int ld_out, c_out_off;             // fp32 rows (may be NULL when the twin is given)
     void* out_split; int lds_out;                  // bf16 hi|lo split twin of `out` (may be NULL)
+    int out_f16;                                   // out_split is an f16 map (PF_PREC_F16 operand) instead
     int relu;
 };
 struct PfFlowStemMulti {

@@ -129,7 +129,8 @@ pf_flow_stem_kernel(const PfFlowStemMulti mm) {
     const long rowbase = (b * H + yy) * (long)W;
     const long p0 = rowbase + x0 + 4 * lh;
     const long plimit = yy < H ? rowbase + W : p0;            // nothing below the map
-    if ((W & 31) != 0 || (H % FS_TR) != 0) tile_epilogue<4, true>(d, acc, 0, li, p0, plimit);
+    if (a.out_f16) tile_epilogue<4, true, true>(d, acc, 0, li, p0, plimit);        // f16 map (mixed_precision)
+    else if ((W & 31) != 0 || (H % FS_TR) != 0) tile_epilogue<4, true>(d, acc, 0, li, p0, plimit);
     else tile_epilogue<4, false>(d, acc, 0, li, p0, 0);
 }
 

@@ -29,4 +29,19 @@ __device__ __forceinline__ void pf_split_store_n(char* p, const float (&v)[N]) {
     *reinterpret_cast<bfN*>(p) = hi;
     *reinterpret_cast<bfN*>(p + 64) = lo;
 }
+// f16 maps (the PF_PREC_F16 operand format, include/priorflow_hip.h): per pixel row, lds units of 128 bytes, channel c at
+// byte 128 * (c >> 6) + 2 * (c & 63); value = fp16(x), round to nearest even.  Address of element (row, ch):
+__device__ __forceinline__ char* pf_f16_ptr(void* base, long row, int lds, int ch) {
+    return reinterpret_cast<char*>(base) + ((row * lds + (ch >> 6)) * 128 + 2 * (ch & 63));
+}
+__device__ __forceinline__ void pf_f16_store(char* p, float v) { *reinterpret_cast<_Float16*>(p) = (_Float16)v; }
+// N = 4 | 8 consecutive channels starting at a multiple of N: one 2N-byte store
+template <int N>
+__device__ __forceinline__ void pf_f16_store_n(char* p, const float (&v)[N]) {
+    typedef _Float16 hN __attribute__((ext_vector_type(N)));
+    hN h;
+#pragma unroll
+    for (int i = 0; i < N; ++i) h[i] = (_Float16)v[i];
+    *reinterpret_cast<hN*>(p) = h;
+}
 #endif

@@ -24,10 +24,20 @@ import torch
 
 import os
 
-from ._lib import (EPI_GRU_Q, EPI_GRU_ZR, EPI_LINEAR, EPI_RELU, EPI_RELU_RES, PREC_BF16X3, PREC_F32,
-                   ConvDesc, PfError, PfLib)
+from ._lib import (EPI_GRU_Q, EPI_GRU_ZR, EPI_LINEAR, EPI_RELU, EPI_RELU_RES, PREC_BF16X3, PREC_F16, PREC_F32,
+                   ConvDesc, PfError, PfLib, is_f16_map)
 
 CORR_CH = 324
+
+# mixed_precision (PREC_F16 update blocks): the convolutions that run with fp16 operands, as the reference's parameter-name
+# prefixes (core/prior_raft.py:190 wraps both update blocks in autocast; core/update.py).  Everything the engine launches through
+# pf_conv2d in the update blocks; NOT convc1* (the fused lookup combine + 1x1 keeps its bf16x3 arithmetic and writes its output
+# as an f16 map), mask.2 (generic 1x1 kernel, bf16x3), convf1* / conv_conf* / flow_head.conv2 (fp32 VALU kernels).
+F16_CONVS = tuple(f"ODDC.encoder.{n}" for n in ("convc2_A", "convf2_A", "convf2_B", "conv_A")) + \
+    tuple(f"update_block.encoder.{n}" for n in ("convc2", "convf2", "conv")) + \
+    tuple(f"{blk}.{n}" for blk in ("ODDC", "update_block")
+          for n in ("gru.convz1", "gru.convr1", "gru.convq1", "gru.convz2", "gru.convr2", "gru.convq2",
+                    "flow_head.conv1", "mask.0"))
 
 
 def rotation_x(theta: float) -> torch.Tensor:
@@ -69,6 +79,21 @@ def split_twin(rows: int, channels: int, device) -> torch.Tensor:
     32-channel chunk the hi halves then the lo halves (include/priorflow_hip.h, pf_conv_desc).  Channels past `channels`
     stay zero: they are the zero padding of the K dimension."""
     return torch.zeros(rows, (channels + 31) // 32, 2, 32, dtype=torch.bfloat16, device=device)
+
+
+def f16_map(rows: int, channels: int, device) -> torch.Tensor:
+    """Zero-initialised f16 map of a channel-last map [rows][channels] (PF_PREC_F16 operand, include/priorflow_hip.h): float16
+    [rows][ceil(channels/64) * 64].  Channels past `channels` stay zero: they are the zero padding of the K dimension."""
+    return torch.zeros(rows, (channels + 63) // 64 * 64, dtype=torch.float16, device=device)
+
+
+def pack_f16(wp: torch.Tensor) -> torch.Tensor:
+    """fp32 [Cout_pad][taps][Cin_pad32] -> fp16 [Cout_pad][taps][Cin_pad64] (round to nearest even, zero filled): the weight
+    operand of PF_PREC_F16."""
+    cp = (wp.shape[-1] + 63) // 64 * 64
+    out = torch.zeros(wp.shape[:-1] + (cp,), dtype=torch.float16, device=wp.device)
+    out[..., :wp.shape[-1]] = wp.half()
+    return out.contiguous()
 
 
 _ZERO_BLOCKS: Dict[str, torch.Tensor] = {}
@@ -143,6 +168,8 @@ class Conv:
         self.precision = precision
         if precision == PREC_BF16X3 and not presplit:
             self.w = split_bf16(w)
+        elif precision == PREC_F16:
+            self.w = pack_f16(w)
 
     @staticmethod
     def of(mod, precision=PREC_F32, cin_to: int = 0) -> "Conv":
@@ -198,8 +225,9 @@ class Conv:
     def desc(self, in0, off0, c0, out, off_out, epilogue, in1=None, off1=0, c1=0, scale=1.0,
              h=None, z=None, aux=None, stride=1, in_scale=None, in_shift=None, in_relu=False,
              stats=None, in0s=None, in1s=None, outs=None, auxs=None, pre=None, off_pre=0, save_gates=False) -> ConvDesc:
-        """in0s / in1s / outs / auxs: optional split twins (``split_twin``) of in0 / in1 / out / aux; with a twin given the
-        fp32 tensor may be None (operands: the all-DMA kernel reads only the twins; outputs: twin only)."""
+        """in0s / in1s / outs / auxs: optional split twins (``split_twin``) of in0 / in1 / out / aux -- f16 maps (``f16_map``)
+        for a PREC_F16 conv; with one given the fp32 tensor may be None (operands: the all-DMA kernel reads only the twins;
+        outputs: twin only)."""
         assert c0 + c1 == self.cin, (c0, c1, self.cin)
         d = ConvDesc()
         # row buffers may be column-sliced views of wider ones: the row stride, not the view's width, is the leading dimension
@@ -211,18 +239,20 @@ class Conv:
         d.weight, d.bias = self.w.data_ptr(), self.b.data_ptr()
         d.out = out.data_ptr() if out is not None else None
         d.ld_out, d.off_out, d.cout = ld(out), off_out, self.cout
+        f16 = self.precision == PREC_F16
         for name, t in (("in0_split", in0s), ("in1_split", in1s), ("out_split", outs), ("aux_split", auxs)):
             if t is not None:
-                assert t.dtype == torch.bfloat16 and t.dim() == 4 and t.shape[2:] == (2, 32) and t.is_contiguous(), name
+                if f16:
+                    assert is_f16_map(t) and t.dim() == 2 and t.shape[1] % 64 == 0 and t.is_contiguous(), name
+                else:
+                    assert t.dtype == torch.bfloat16 and t.dim() == 4 and t.shape[2:] == (2, 32) and t.is_contiguous(), name
                 setattr(d, name, t.data_ptr())
+        units = (lambda t: 0 if t is None else t.shape[1] // 64) if f16 else (lambda t: 0 if t is None else t.shape[1])  # noqa: E731
         zb = None
         if in0s is not None:           # the zero padding of an all-DMA launch is read from memory
             zb = _zero_block(in0s.device)
             d.zeros, d.zeros_bytes = zb.data_ptr(), zb.numel() * 4
-        d.lds0 = in0s.shape[1] if in0s is not None else 0
-        d.lds1 = in1s.shape[1] if in1s is not None else 0
-        d.lds_out = outs.shape[1] if outs is not None else 0
-        d.lds_aux = auxs.shape[1] if auxs is not None else 0
+        d.lds0, d.lds1, d.lds_out, d.lds_aux = units(in0s), units(in1s), units(outs), units(auxs)
         d.kh, d.kw, d.epilogue, d.scale = self.kh, self.kw, epilogue, scale
         d.h = h.data_ptr() if h is not None else None
         d.ld_h = ld(h)
@@ -252,17 +282,20 @@ class DirectConv:
 
 
 def pack_update_blocks(oddc, upd, precision: Optional[int] = None) -> Dict[str, object]:
+    """precision PREC_F16 (mixed_precision): the convolutions of F16_CONVS get fp16 weights; the fused combine + convc1 and
+    mask.2 keep the bf16x3 packing."""
     pr = default_precision() if precision is None else precision
+    pr_x = PREC_BF16X3 if pr == PREC_F16 else pr      # convc1 (fused with the lookup combine) and mask.2
     C = lambda m: Conv.of(m, pr)                      # noqa: E731
     ea, eb = oddc.encoder, upd.encoder
     P: Dict[str, object] = {
         "precision": pr,
-        "a.c1": C(ea.convc1_A), "a.c2": C(ea.convc2_A),
+        "a.c1": Conv.of(ea.convc1_A, pr_x), "a.c2": C(ea.convc2_A),
         "a.f1a": DirectConv(ea.convf1_A), "a.f2a": C(ea.convf2_A),
         "a.f1b": DirectConv(ea.convf1_B), "a.f2b": C(ea.convf2_B),
         "a.cf1": DirectConv(ea.conv_conf1), "a.cf2": DirectConv(ea.conv_conf2),
         "a.out": C(ea.conv_A),
-        "b.c1": C(eb.convc1), "b.c2": C(eb.convc2),
+        "b.c1": Conv.of(eb.convc1, pr_x), "b.c2": C(eb.convc2),
         # branch B's conv sees its 256-channel concat zero-padded to 272 so that it shares the
         # launch geometry (K = 9 x 272) of branch A's conv_A: one grid instead of two half-empty ones
         "b.f1": DirectConv(eb.convf1), "b.f2": C(eb.convf2), "b.out": Conv.of(eb.conv, pr, cin_to=272),
@@ -273,7 +306,7 @@ def pack_update_blocks(oddc, upd, precision: Optional[int] = None) -> Dict[str, 
         P[f"{tag}.q1"] = C(g.convq1)
         P[f"{tag}.zr2"] = Conv.fused(g.convz2, g.convr2, pr)
         P[f"{tag}.q2"] = C(g.convq2)
-        if pr == PREC_BF16X3:
+        if pr in (PREC_BF16X3, PREC_F16):
             # context hoist (Engine.hoist_context): GRU input = [h 0:128 | inp 128:256 | motion 256:384]; `inp` does not change
             # over the iterations, so its part of all three gates is ONE 128 -> 384 conv per half-step, run once per forward
             # (with the biases), and the per-iteration convs see [h | motion] only
@@ -287,7 +320,7 @@ def pack_update_blocks(oddc, upd, precision: Optional[int] = None) -> Dict[str, 
         P[f"{tag}.fh2w"] = w2.permute(0, 2, 3, 1).reshape(2, 9, w2.shape[1]).contiguous()
         P[f"{tag}.fh2b"] = blk.flow_head.conv2.bias.detach().float().contiguous()
         P[f"{tag}.m0"] = C(blk.mask[0])
-        P[f"{tag}.m2"] = C(blk.mask[2])
+        P[f"{tag}.m2"] = Conv.of(blk.mask[2], pr_x)
     return P
 
 
@@ -295,11 +328,14 @@ def pack_update_blocks(oddc, upd, precision: Optional[int] = None) -> Dict[str, 
 class Workspace:
     """All device buffers of one (B, H, W) problem; allocated once, reused every call."""
 
-    def __init__(self, lib: PfLib, B: int, H: int, W: int, device):
+    def __init__(self, lib: PfLib, B: int, H: int, W: int, device, f16: bool = False):
+        """f16: the update blocks run in PREC_F16 -- their operand buffers (the ``*_s`` attributes) are f16 maps instead of split
+        twins; fnet's features for the corr build stay split twins."""
         if H % 8 or W % 8 or H < 128 or W < 128:
             raise PfError(f"image size {H}x{W}: H and W must be multiples of 8 (callers pad, core/utils/utils.py:7-27) "
                           "and at least 128 (the coarsest pyramid level must be 2x2 or larger)")
         self.B, self.H, self.W = B, H, W
+        self.f16 = f16
         self.H8, self.W8 = H // 8, W // 8
         self.N = self.H8 * self.W8
         self.device = device
@@ -363,7 +399,8 @@ class Workspace:
         # ---- split twins (bf16 hi|lo rows, include/priorflow_hip.h): every activation an MFMA conv of the update blocks
         # consumes is written in this form by its producer, so both operands of those convs go global -> LDS by DMA.
         # Only the hidden state keeps an fp32 copy as well (the GRU epilogues blend with it).
-        tw = lambda r, c: split_twin(r, c, device)  # noqa: E731
+        # (f16: the same buffers as f16 maps; cat_* then has 5 units of 64 channels, 320 > 272, its tail zero)
+        tw = (lambda r, c: f16_map(r, c, device)) if f16 else (lambda r, c: split_twin(r, c, device))  # noqa: E731
         self.net0_ab_s = tw(2 * rows, 128)
         self.net_a_s = [self.net0_ab_s[:rows], tw(rows, 128)]
         self.net_b_s = [self.net0_ab_s[rows:], tw(rows, 128)]
@@ -379,6 +416,11 @@ class Workspace:
 
     def sync_twins(self, lib: PfLib):
         """Refresh the twins of the loop's INPUT state from the fp32 buffers (tests that fill net / x by hand)."""
+        if self.f16:
+            for x, m in ((self.net0_ab, self.net0_ab_s), (self.net_a[1], self.net_a_s[1]), (self.net_b[1], self.net_b_s[1]),
+                         (self.x_ab, self.x_ab_s)):
+                lib.split_f16(x, m)
+            return
         lib.split_bf16(self.net0_ab, self.net0_ab_s)
         lib.split_bf16(self.net_a[1], self.net_a_s[1])
         lib.split_bf16(self.net_b[1], self.net_b_s[1])
@@ -418,7 +460,16 @@ class Engine:
         self.split_ab = os.environ.get("PRIORFLOW_SPLIT_AB", "1") != "0"
 
     def presplit(self, P) -> bool:
-        return self.presplit_on and P["precision"] == PREC_BF16X3
+        """Operands of the update blocks' convolutions as split twins / f16 maps (all-DMA kernel).  PREC_F16 exists in that form
+        only (the PRIORFLOW_PRESPLIT=0 A/B knob applies to bf16x3)."""
+        return P["precision"] == PREC_F16 or (self.presplit_on and P["precision"] == PREC_BF16X3)
+
+    @staticmethod
+    def encoder_precision(P) -> int:
+        """Arithmetic of cnet / fnet and the corr build: the update blocks' own, except that PREC_F16 (mixed_precision) is an
+        update-block mode -- the encoders and the correlation keep bf16x3 (the reference computes the correlation in fp32 outside
+        autocast, core/prior_raft.py:146-153)."""
+        return PREC_BF16X3 if P["precision"] == PREC_F16 else P["precision"]
 
     def hoist(self, P) -> bool:
         """Context hoist on: the GRU convs take the iteration-invariant `inp` part from ws.pre (needs the all-DMA kernel)."""
@@ -672,7 +723,8 @@ class Engine:
         A looks into B through grid(R_A2B^T)==grid(R_B2A) and rotates back with grid(R_B2A); B the other way."""
         lib, B, H8, W8 = self.lib, ws.B, ws.H8, ws.W8
         # bf16x3: rotate-back + add + convc1 are ONE launch (pf_dccl_combine_conv1x1): corr_a / corr_b never exist
-        fused = P["precision"] == PREC_BF16X3
+        # (PREC_F16: convc1 keeps the bf16x3 packing, and the launch writes its output as an f16 map)
+        fused = P["a.c1"].precision == PREC_BF16X3
         ps = self.presplit(P)
 
         def look_a():

@@ -19,15 +19,23 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import EncoderPlan, Engine, Workspace, default_precision, pack_update_blocks
+from .engine import EncoderPlan, Engine, Workspace, pack_update_blocks
 from .modules import BasicEncoder, build_tree, state_dict_shapes  # noqa: F401
 
 
 class PriOr_RAFT(nn.Module):
-    """``args.mixed_precision`` is accepted and has no effect: the reference wraps its encoders and update blocks in CUDA
-    autocast (core/prior_raft.py:133,146,190) and scales the loss (train_flow.py:112,136-139); here every GEMM-shaped op runs
-    the 3-pass bf16 split with fp32 accumulation and storage (or exact fp32, ``PRIORFLOW_PRECISION=fp32``), which needs neither.
-    ``args.dropout`` is honoured by the training forward."""
+    """By default every GEMM-shaped op runs the 3-pass bf16 split with fp32 accumulation and storage (or exact fp32,
+    ``PRIORFLOW_PRECISION=fp32``).
+
+    ``args.mixed_precision=True`` (or ``model.precision = PREC_F16``) selects the fp16 update blocks for the inference forward,
+    eager and graph replay: the reference runs its update blocks under CUDA autocast (core/prior_raft.py:190), and here every
+    update-block convolution of ``engine.F16_CONVS`` runs single-pass on the matrix cores with fp16 operands (the activation
+    rounded to nearest-even fp16 from its fp32 value, ``weight.half()``) and fp32 accumulation; biases, epilogues, the GRU
+    state, the flow and everything else stay fp32.  convc1 (fused with the lookup combine) and mask.2 keep bf16x3, the 7x7 /
+    confidence stems and flow_head.conv2 fp32.  The encoders and the corr build keep bf16x3 (the reference's autocast over the
+    encoders, :133, is not followed; the correlation is fp32 there, :146-153).  The training forward (``train()`` with autograd)
+    keeps its bf16x3 arithmetic whatever the flag says: fp16 training with loss scaling (train_flow.py:112,136-139) is not
+    implemented.  ``args.dropout`` is honoured by the training forward."""
 
     def __init__(self, args):
         super().__init__()
@@ -46,7 +54,7 @@ class PriOr_RAFT(nn.Module):
         self._enc_plans = None
         self._enc_sig = None
         self.use_graph = os.environ.get("PRIORFLOW_GRAPH", "1") != "0"
-        self.precision: Optional[int] = None      # None -> PRIORFLOW_PRECISION env (default bf16x3)
+        self.precision: Optional[int] = None      # None -> args.mixed_precision (PREC_F16), else PRIORFLOW_PRECISION (default bf16x3)
         self.use_streams = os.environ.get("PRIORFLOW_STREAMS", "1") != "0"
         self._side_streams = None
 
@@ -78,12 +86,20 @@ class PriOr_RAFT(nn.Module):
     def _lib(self) -> _lib.PfLib:
         return _lib.load()       # raises loudly when the HIP library is missing
 
+    def _update_precision(self) -> Optional[int]:
+        """Arithmetic of the update blocks: ``model.precision`` when set, PREC_F16 for ``args.mixed_precision``, else None
+        (PRIORFLOW_PRECISION)."""
+        if self.precision is not None:
+            return self.precision
+        return _lib.PREC_F16 if getattr(self.args, "mixed_precision", False) else None
+
     def _weights(self):
         params = list(self.ODDC.parameters()) + list(self.update_block.parameters())
-        sig = tuple((p.data_ptr(), p._version) for p in params) + (self.precision, _lib.weights_epoch())
+        pr = self._update_precision()
+        sig = tuple((p.data_ptr(), p._version) for p in params) + (pr, _lib.weights_epoch())
         if self._packed is None or sig != self._packed_sig:
             with torch.no_grad():
-                self._packed = pack_update_blocks(self.ODDC, self.update_block, self.precision)
+                self._packed = pack_update_blocks(self.ODDC, self.update_block, pr)
             self._packed_sig = sig
             self._graphs.clear()
         return self._packed
@@ -95,10 +111,16 @@ class PriOr_RAFT(nn.Module):
         """The buffers of one (B, H, W) problem.  A few shapes stay resident, least recently used first out, together with the
         HIP graphs captured on them: an evaluation loop over mixed sizes (or B = 1 / B = 32 in turn) re-uses its workspaces and
         graphs instead of re-allocating ~1 GB and re-capturing 258 kernels per switch."""
+        f16 = self._weights()["precision"] == _lib.PREC_F16          # the update blocks' operands as f16 maps
         key = (B, H, W, str(device))
         ws = self._ws.pop(key, None)
+        if ws is not None and ws.f16 != f16:
+            # mixed_precision was switched: the operand buffers of the update blocks change form (twins <-> f16 maps)
+            for gk in [gk for gk in self._graphs if (gk[0], gk[1], gk[2], gk[4]) == key]:
+                del self._graphs[gk]
+            ws = None
         if ws is None:
-            ws = Workspace(self._lib(), B, H, W, device)
+            ws = Workspace(self._lib(), B, H, W, device, f16=f16)
             ws.nbytes = sum(t.numel() * t.element_size() for t in vars(ws).values() if isinstance(t, torch.Tensor)) + \
                 sum(t.numel() * t.element_size() for v in vars(ws).values() if isinstance(v, (list, tuple))
                     for t in v if isinstance(t, torch.Tensor))
@@ -116,8 +138,9 @@ class PriOr_RAFT(nn.Module):
         return ws
 
     def _encoder_plans(self):
-        """HIP launch plans of cnet / fnet (either precision), rebuilt when their weights or the precision change."""
-        precision = default_precision() if self.precision is None else self.precision
+        """HIP launch plans of cnet / fnet (either precision), rebuilt when their weights or the precision change.  (The fp16
+        update blocks of mixed_precision leave the encoders on bf16x3: Engine.encoder_precision.)"""
+        precision = Engine.encoder_precision(self._weights())
         params = list(self.fnet.parameters()) + list(self.cnet.parameters()) + list(self.cnet.buffers())
         sig = tuple((p.data_ptr(), p._version) for p in params) + (_lib.weights_epoch(), precision)
         if self._enc_plans is None or sig != self._enc_sig:
@@ -140,13 +163,21 @@ class PriOr_RAFT(nn.Module):
         cplan, fplan = self._encoder_plans()       # both precisions run on the HIP library: there is no PyTorch-ROCm branch
         # context features: net (fp32 + split twin) and inp (first 128 columns of the GRU input x; twin only when the
         # update blocks run on pre-split activations)
-        ctx = dict(outs=ws.net0_ab_s, auxs=ws.x_ab_s) if eng.presplit(self._weights()) else dict(aux=ws.x_ab)
+        # (f16 update blocks: cnet writes fp32 rows and pf_split_f16 makes the maps, ctx_f16 below)
+        f16 = ws.f16
+        ctx = dict(outs=ws.net0_ab_s, auxs=ws.x_ab_s) if eng.presplit(self._weights()) and not f16 else dict(aux=ws.x_ab)
+
+        def ctx_f16():
+            if f16:
+                lib = self._lib()
+                lib.split_f16(ws.net0_ab, ws.net0_ab_s)
+                lib.split_f16(ws.x_ab[:, :128], ws.x_ab_s)
         # fnet's last convolution (1x1 128 -> 256) writes the features twice: fp32 rows (the warps' operand) and the bf16 hi|lo
         # rows the corr GEMM multiplies -- the epilogue's twin equals pf_split_bf16 of the fp32 rows bit for bit, and the
         # separate split launch (21-37 us of kernel time between the encoders and the corr build) is gone (round 6; the forward's
         # wall time did not move: 147.1 against 147.2 pairs/s, profiles/r6_ab_head.txt -- the stretch overlaps cnet's tail)
         from ._lib import PREC_BF16X3
-        fsplit = dict(outs=ws.f_split) if self._weights()["precision"] == PREC_BF16X3 and fplan.precision == PREC_BF16X3 else {}
+        fsplit = dict(outs=ws.f_split) if Engine.encoder_precision(self._weights()) == PREC_BF16X3 and fplan.precision == PREC_BF16X3 else {}
         ws.f_split_ready = bool(fsplit)
         P = self._weights()
         if self.use_streams and int(os.environ.get("PRIORFLOW_FORKS", "15")) & 1:
@@ -162,6 +193,7 @@ class PriOr_RAFT(nn.Module):
             ev = torch.cuda.Event()
             ev.record(cur)
             cplan.run(ws.img_c, ws.net0_ab, EPI_TANH_RELU, **ctx)
+            ctx_f16()
             eng.hoist_context(ws, P)
             s1.wait_event(ev)
             with torch.cuda.stream(s1):
@@ -169,7 +201,7 @@ class PriOr_RAFT(nn.Module):
                 # the corr volumes + pyramids need fnet's features only: on fnet's queue, right behind its last convolution (the
                 # hop back to the calling stream cost 14 us in front of the first corr launch; cnet and the hoisted
                 # convolutions are long done by then, so the launches still have the chip to themselves)
-                eng.build_pyramids(ws, P["precision"])
+                eng.build_pyramids(ws, Engine.encoder_precision(P))
             # coords1 = coords0 (+ init_flow): two small copies nobody needs before the first lookup -- on a queue of their own,
             # not in front of cnet's stem (19 us of an otherwise idle chip at the head of every forward)
             s2.wait_event(ev)
@@ -180,9 +212,10 @@ class PriOr_RAFT(nn.Module):
         else:
             eng.init_coords(ws, init_flow)
             cplan.run(ws.img_c, ws.net0_ab, EPI_TANH_RELU, **ctx)
+            ctx_f16()
             fplan.run(ws.img_f, ws.f_all, EPI_LINEAR, **fsplit)
             eng.hoist_context(ws, P)               # iteration-invariant part of the GRU convs (pre-split path only)
-            eng.build_pyramids(ws, P["precision"])
+            eng.build_pyramids(ws, Engine.encoder_precision(P))
 
     def _streams(self):
         if self._side_streams is None:
