@@ -141,6 +141,29 @@ int pf_dccl_lookup_il(const float* coords,
                       const float* g_w2c, const float* g_w2c_il, float* own_out, float* raw_out,
                       int B, int H8, int W8, int ld, void* stream);
 
+/* alternate_corr (AlternateCorrBlock, core/corr.py:64-91): the lookups without the correlation volumes.
+ *
+ * pf_feature_pyramid: levels 1-3 of f2 pooled, channel-last [B*N_i][C] rows, N_i = (H8>>i)*(W8>>i).  Level i+1 is
+ * the 2x2 mean of level i with avg_pool2d floor semantics (odd sizes drop the last row / column).  Level 0 is f2.
+ *
+ * pf_dccl_lookup_feat: the outputs of pf_dccl_lookup(coords, pyr(f1_own, f2_own), pyr(f1_oth, f2_oth), g_w2c, ...),
+ * up to rounding, computed from the features: level i of the pyramid at (n, p) is <f1[n], P_i(f2)[p]> / sqrt(C), so
+ * every bilinear corner is one C-long fp32 dot product at lookup time.  f1_* / f2_*0: channel-last [B*N][C];
+ * f2_*1..3: pf_feature_pyramid's levels.  Same 324-channel layout, row stride ld >= 324 (columns >= 324 are not
+ * written) and semantics: x wrapped mod W_i then zero padded; the cross view samples the LEVEL-0 grid at level-i
+ * coordinates and uses the result un-scaled at level i; raw row n correlates the OTHER branch's f1[n].
+ * path_counts: NULL, or a device int[2] the kernel adds to: (tile, level, view) units whose corners were computed from
+ * window rows staged in LDS once per tile of neighbouring pixels [0], or per pixel from global memory [1] (the host
+ * emulation leaves it untouched).
+ * Both: C % 4 == 0, C <= 512, level 3 at least 2x2, feature pointers 16-byte aligned. */
+int pf_feature_pyramid(const float* f2, float* l1, float* l2, float* l3, int B, int H8, int W8, int C, void* stream);
+int pf_dccl_lookup_feat(const float* coords, const float* f1_own,
+                        const float* f2_own0, const float* f2_own1, const float* f2_own2, const float* f2_own3,
+                        const float* f1_oth,
+                        const float* f2_oth0, const float* f2_oth1, const float* f2_oth2, const float* f2_oth3,
+                        const float* g_w2c, float* own_out, float* raw_out, int* path_counts,
+                        int B, int H8, int W8, int C, int ld, void* stream);
+
 
 /* DCCL.__call__ step 3 + the caller's add (core/corr.py:138, core/prior_raft.py:187-188):
  * out = own + img_rotate(raw, g_back), channel-last. */

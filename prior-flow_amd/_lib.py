@@ -103,6 +103,8 @@ _SIGNATURES = {
     "pf_bn_frozen_bwd": [_fp, _fp, _fp, _fp, _fp, _fp, C.c_float, _i, _fp, _i, _fp, _fp, _fp, _i, C.c_long, _i, _fp],
     "pf_dccl_lookup": [_fp] * 12 + [_i, _i, _i, _i, _fp],
     "pf_dccl_lookup_il": [_fp] * 13 + [_i, _i, _i, _i, _fp],
+    "pf_feature_pyramid": [_fp] * 4 + [_i, _i, _i, _i, _fp],
+    "pf_dccl_lookup_feat": [_fp] * 15 + [_i, _i, _i, _i, _i, _fp],
     "pf_dccl_combine": [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp],
     "pf_warp_gcorr": [_fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _i, _fp],
     "pf_conf_stem": [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _fp],
@@ -193,6 +195,14 @@ def _one_form(*maps) -> bool:
     if len(kinds) > 1:
         raise PfError("split twins and f16 maps mixed in one launch")
     return kinds == {True}
+
+
+def _feat_shapes(levels, B, H8, W8, C, what):
+    """alternate_corr: feature level i is channel-last [B*(H8>>i)*(W8>>i), C] (the kernels read that many rows)."""
+    for i, t in enumerate(levels):
+        want = (B * (H8 >> i) * (W8 >> i), C)
+        if t.dim() != 2 or tuple(t.shape) != want:
+            raise PfError(f"{what}: feature level {i} is {tuple(t.shape)}, expected {want}")
 
 
 class PfLib:
@@ -435,6 +445,39 @@ class PfLib:
             _ptr(coords), *[_ptr(p) for p in pyr_own], *[_ptr(p) for p in pyr_other],
             _ptr(g_w2c), _ptr(g_il), _ptr(own_out), _ptr(raw_out), B, H, W, own_out.shape[-1],
             self._stream(coords)), "pf_dccl_lookup_il")
+
+    def feature_pyramid(self, f2, levels, B, H8, W8):
+        """alternate_corr: f2 channel-last [B*N, C] -> levels 1-3 [B*N_i, C] (2x2 floor means, ``pf_feature_pyramid``)."""
+        self._chk(f2, *levels)
+        if len(levels) != 3:
+            raise PfError("feature_pyramid: three pooled levels (1-3); level 0 is f2 itself")
+        _feat_shapes([f2, *levels], B, H8, W8, f2.shape[-1], "feature_pyramid")
+        self._rc(self._dll.pf_feature_pyramid(_ptr(f2), *[_ptr(l) for l in levels], B, H8, W8, f2.shape[-1],
+                                              self._stream(f2)), "pf_feature_pyramid")
+
+    def dccl_lookup_feat(self, coords, f1_own, f2_own, f1_oth, f2_oth, g_w2c, own_out, raw_out, path_counts=None):
+        """alternate_corr form of ``dccl_lookup``: f2_own / f2_oth are the four feature levels [f2, l1, l2, l3]
+        (``feature_pyramid``) instead of the four volume levels.  path_counts: optional int32 [2] the kernel adds its
+        (tile, level, view) units on the LDS-tile path [0] and on the per-pixel path [1] to."""
+        self._chk(coords, f1_own, f1_oth, g_w2c, own_out, raw_out, *f2_own, *f2_oth)
+        if len(f2_own) != 4 or len(f2_oth) != 4:
+            raise PfError("dccl_lookup_feat: four feature levels per view")
+        B, _, H, W = coords.shape
+        C = f1_own.shape[-1]
+        for f in (f2_own, f2_oth):
+            _feat_shapes(f, B, H, W, C, "dccl_lookup_feat")
+        for t in (f1_own, f1_oth, own_out, raw_out):
+            if t.dim() != 2 or t.shape[0] != B * H * W:
+                raise PfError(f"dccl_lookup_feat: rows of {tuple(t.shape)} do not match B*H8*W8 = {B * H * W}")
+        if f1_oth.shape[-1] != C or g_w2c.numel() != 2 * H * W:
+            raise PfError("dccl_lookup_feat: f1_oth / g_w2c do not fit coords and f1_own")
+        if path_counts is not None and (path_counts.dtype != torch.int32 or path_counts.numel() < 2
+                                        or not path_counts.is_contiguous()):
+            raise PfError("dccl_lookup_feat: path_counts is a contiguous int32 tensor of 2 elements")
+        self._rc(self._dll.pf_dccl_lookup_feat(
+            _ptr(coords), _ptr(f1_own), *[_ptr(p) for p in f2_own], _ptr(f1_oth), *[_ptr(p) for p in f2_oth],
+            _ptr(g_w2c), _ptr(own_out), _ptr(raw_out), _ptr(path_counts), B, H, W, C, own_out.shape[-1],
+            self._stream(coords)), "pf_dccl_lookup_feat")
 
     def dccl_combine(self, own, raw, g_back, out, B, H8, W8):
         self._chk(own, raw, g_back, out)

@@ -93,6 +93,49 @@ extern "C" int pf_dccl_lookup(const float* coords, const float* own0, const floa
                              B, H8, W8, ld, stream);
 }
 
+// alternate_corr (pf_elem.h: pf_feat_pool_elem, pf_lookup_feat_elem)
+#ifndef PF_LOOKUP_FEAT_LAUNCH
+#define PF_LOOKUP_FEAT_LAUNCH(a, total, stream) PF_LAUNCH(lookup_feat, a, total, stream)
+#endif
+static inline bool pf_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// the pooled levels' sizes must reach a 2x2 level 3 (the (size-1) normalisation of the sampler divides by zero otherwise);
+// C: the tuned kernel holds a lane's channels in registers (4 per 256)
+#define PF_FEAT_SHAPE_OK(B, H8, W8, C) ((B) > 0 && ((H8) >> 3) >= 2 && ((W8) >> 3) >= 2 && (C) > 0 && (C) % 4 == 0 && (C) <= 512)
+
+extern "C" int pf_feature_pyramid(const float* f2, float* l1, float* l2, float* l3, int B, int H8, int W8, int C,
+                                  void* stream) {
+    PF_REQUIRE(f2 && l1 && l2 && l3);
+    PF_REQUIRE(pf_aligned16(f2) && pf_aligned16(l1) && pf_aligned16(l2) && pf_aligned16(l3));
+    PF_REQUIRE_SHAPE(PF_FEAT_SHAPE_OK(B, H8, W8, C));
+    const float* in[3] = {f2, l1, l2};
+    float* out[3] = {l1, l2, l3};
+    for (int i = 0; i < 3; ++i) {
+        PfFeatPoolArgs a; a.in = in[i]; a.out = out[i]; a.B = B; a.H = H8 >> i; a.W = W8 >> i; a.C = C;
+        const int rc = PF_LAUNCH(feat_pool, a, (long)B * (a.H >> 1) * (a.W >> 1) * (C / 4), stream);
+        if (rc != PF_OK) return rc;
+    }
+    return PF_OK;
+}
+
+extern "C" int pf_dccl_lookup_feat(const float* coords, const float* f1_own, const float* f2_own0, const float* f2_own1,
+                                   const float* f2_own2, const float* f2_own3, const float* f1_oth, const float* f2_oth0,
+                                   const float* f2_oth1, const float* f2_oth2, const float* f2_oth3, const float* g_w2c,
+                                   float* own_out, float* raw_out, int* path_counts, int B, int H8, int W8, int C, int ld,
+                                   void* stream) {
+    PF_REQUIRE(coords && f1_own && f2_own0 && f2_own1 && f2_own2 && f2_own3);
+    PF_REQUIRE(f1_oth && f2_oth0 && f2_oth1 && f2_oth2 && f2_oth3);
+    PF_REQUIRE(g_w2c && own_out && raw_out && own_out != raw_out);
+    const float* fs[10] = {f1_own, f2_own0, f2_own1, f2_own2, f2_own3, f1_oth, f2_oth0, f2_oth1, f2_oth2, f2_oth3};
+    for (int i = 0; i < 10; ++i) PF_REQUIRE(pf_aligned16(fs[i]));
+    PF_REQUIRE_SHAPE(PF_FEAT_SHAPE_OK(B, H8, W8, C) && ld >= PF_CORR_CH);
+    PfLookupFeatArgs a; a.coords = coords; a.f1_own = f1_own; a.f1_oth = f1_oth;
+    a.f2_own[0] = f2_own0; a.f2_own[1] = f2_own1; a.f2_own[2] = f2_own2; a.f2_own[3] = f2_own3;
+    a.f2_oth[0] = f2_oth0; a.f2_oth[1] = f2_oth1; a.f2_oth[2] = f2_oth2; a.f2_oth[3] = f2_oth3;
+    a.g_w2c = g_w2c; a.own_out = own_out; a.raw_out = raw_out; a.path_counts = path_counts;
+    a.B = B; a.H = H8; a.W = W8; a.C = C; a.ld = ld; a.scale = 1.f / sqrtf((float)C);
+    return PF_LOOKUP_FEAT_LAUNCH(a, (long)B * H8 * W8 * PF_CORR_CH, stream);
+}
+
 extern "C" int pf_dccl_combine(const float* own, const float* raw, const float* g_back, float* out,
                                int B, int H8, int W8, int ld, int ld_out, void* stream) {
     PF_REQUIRE(own && raw && g_back && out && out != raw);

@@ -498,6 +498,92 @@ PF_HD void pf_lookup_elem(long idx, const PfLookupArgs& a) {  // idx over B*N*(3
     }
 }
 
+// ----------------------------------------------------------------------------------------------
+// alternate_corr: the same two lookups without the correlation volumes (AlternateCorrBlock, core/corr.py:64-91).
+// Pooling is linear, so level i of the pyramid at (n, p) is <f1[n], P_i(f2)[p]> / sqrt(C), P_i = the 2x2 floor mean of
+// f2 applied i times (pf_feature_pyramid).  Each bilinear corner is one C-long dot product computed at lookup time.
+// ----------------------------------------------------------------------------------------------
+struct PfFeatPoolArgs {
+    const float* in;                // channel-last [B*H*W][C]
+    float* out;                     // channel-last [B*(H/2)*(W/2)][C]
+    int B, H, W, C;
+};
+PF_HD void pf_feat_pool_elem(long idx, const PfFeatPoolArgs& a) {     // idx over B*(H/2)*(W/2)*(C/4)
+    const int C4 = a.C / 4, Ho = a.H >> 1, Wo = a.W >> 1;
+    const long c = (idx % C4) * 4;
+    const long p = idx / C4;
+    const long b = p / ((long)Ho * Wo), q = p % ((long)Ho * Wo);
+    const long y = q / Wo, x = q % Wo;
+    const float* r0 = a.in + ((b * a.H + 2 * y) * a.W + 2 * x) * a.C + c;   // (2y, 2x); odd sizes drop the last row / column
+    const float* r2 = r0 + (long)a.W * a.C;
+    float* o = a.out + p * a.C + c;
+    for (int j = 0; j < 4; ++j) o[j] = (((r0[j] + r0[a.C + j]) + r2[j]) + r2[a.C + j]) * 0.25f;
+}
+
+struct PfLookupFeatArgs {
+    const float* coords;                    // planar [B,2,N]
+    const float* f1_own;                    // channel-last [B*N][C]
+    const float* f2_own[PF_CORR_LEVELS];    // level i: channel-last [B*N_i][C] (level 0: f2 itself)
+    const float* f1_oth;
+    const float* f2_oth[PF_CORR_LEVELS];
+    const float* g_w2c;                     // [2,N]
+    float* own_out;                         // channel-last [B*N][ld]
+    float* raw_out;
+    int* path_counts;                       // optional [2]: (tile, level, view) units on the tile / pixel path (device kernel only)
+    int B, H, W, C, ld;
+    float scale;                            // 1 / sqrt(C)
+};
+PF_HD float pf_feat_dot(const float* x, const float* y, int C) {
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s = s + x[c] * y[c];
+    return s;
+}
+// element index of the four corners of a zero-padded bilinear sample (the picks of pf_apply_pairs), -1 where the weight is 0
+PF_HD void pf_taps2_corners(const PfTaps2& t, int (&e)[4]) {
+    e[0] = t.w[0] != 0.f ? t.r0 + (t.s0hi ? 1 : 0) : -1;
+    e[1] = t.w[1] != 0.f ? t.r0 + (t.s1lo ? 0 : 1) : -1;
+    e[2] = t.w[2] != 0.f ? t.r1 + (t.s0hi ? 1 : 0) : -1;
+    e[3] = t.w[3] != 0.f ? t.r1 + (t.s1lo ? 0 : 1) : -1;
+}
+// bilinear sample of the level volume row <f1, f2l[.]> * scale; corners with weight 0 contribute 0 (the volume is finite)
+PF_HD float pf_feat_sample(const PfTaps2& t, const float* f1, const float* f2l, int C, float scale) {
+    int e[4];
+    pf_taps2_corners(t, e);
+    float v[4];
+    for (int j = 0; j < 4; ++j) v[j] = e[j] < 0 ? 0.f : pf_feat_dot(f1, f2l + (long)e[j] * C, C) * scale;
+    float acc = v[0] * t.w[0];
+    acc = acc + v[1] * t.w[1];
+    acc = acc + v[2] * t.w[2];
+    acc = acc + v[3] * t.w[3];
+    return acc;
+}
+// The tap geometry of pf_lookup_elem: own view x wrapped mod W_i, zero padded; the cross view samples the LEVEL-0 grid at
+// level-i coordinates and uses the result un-scaled at level i; raw row n correlates the OTHER branch's f1[n].
+PF_HD PfTaps2 pf_lookup_feat_tap(const PfLookupFeatArgs& a, long b, long n, int lvl, int tap, bool cross) {
+    const long N = (long)a.H * a.W;
+    const int ta = tap / 9, tb = tap % 9;
+    const int Hl = a.H >> lvl, Wl = a.W >> lvl;
+    const float inv = 1.f / (float)(1 << lvl);                     // coords / 2**i : exact
+    const float cx = a.coords[(b * 2 + 0) * N + n] * inv + (float)(ta - PF_CORR_RADIUS);
+    const float cy = a.coords[(b * 2 + 1) * N + n] * inv + (float)(tb - PF_CORR_RADIUS);
+    if (!cross) return pf_taps0v(pf_pymod(cx, (float)Wl), cy, Hl, Wl);
+    const PfTaps2 tg = pf_taps0v(pf_pymod(cx, (float)a.W), cy, a.H, a.W);
+    const float gx = pf_apply_v(tg, a.g_w2c), gy = pf_apply_v(tg, a.g_w2c + N);
+    return pf_taps0v(pf_pymod(gx, (float)Wl), gy, Hl, Wl);
+}
+PF_HD void pf_lookup_feat_elem(long idx, const PfLookupFeatArgs& a) {  // idx over B*N*324
+    const long N = (long)a.H * a.W;
+    const int k = (int)(idx % PF_CORR_CH);
+    const long row = idx / PF_CORR_CH;
+    const long b = row / N, n = row % N;
+    const int lvl = k / PF_TAPS;
+    const long lsz = (long)(a.H >> lvl) * (a.W >> lvl);
+    const PfTaps2 to = pf_lookup_feat_tap(a, b, n, lvl, k % PF_TAPS, false);
+    const PfTaps2 tc = pf_lookup_feat_tap(a, b, n, lvl, k % PF_TAPS, true);
+    a.own_out[row * a.ld + k] = pf_feat_sample(to, a.f1_own + row * a.C, a.f2_own[lvl] + b * lsz * a.C, a.C, a.scale);
+    a.raw_out[row * a.ld + k] = pf_feat_sample(tc, a.f1_oth + row * a.C, a.f2_oth[lvl] + b * lsz * a.C, a.C, a.scale);
+}
+
 // K4(c): rotate the raw cross-view lookup back and add the own-view lookup
 // (core/corr.py:138; core/prior_raft.py:187-188).
 struct PfCombineArgs {

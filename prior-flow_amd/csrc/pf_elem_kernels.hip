@@ -1228,6 +1228,9 @@ static int pf_lookup_dispatch(const PfLookupArgs& a, long total, void* stream) {
 }
 #define PF_LOOKUP_LAUNCH(a, total, stream) pf_lookup_dispatch(a, total, stream)
 #endif
+// alternate_corr: the wave-per-(pixel, level) kernel of pf_lookup.hip (pf_lookup_feat_elem is the host emulation's statement)
+int pf_lookup_feat_launch(const PfLookupFeatArgs& a, void* stream);
+#define PF_LOOKUP_FEAT_LAUNCH(a, total, stream) pf_lookup_feat_launch(a, stream)
 #define PF_REGION_SUM_LAUNCH(a, stream) launch_region_sums(a, stream)
 #define PF_SEQ_LOSS_LAUNCH(a, stream) launch_seq_loss(a, stream)
 #define PF_SEQ_LOSS_BATCH_LAUNCH(t, stream) launch_seq_loss_batch(t, stream)

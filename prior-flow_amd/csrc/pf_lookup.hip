@@ -203,3 +203,205 @@ int pf_lookup_win_launch(const PfLookupArgs& a, void* stream) {
     hipLaunchKernelGGL(pf_lookup_win_kernel, dim3((unsigned)blocks), dim3(64 * LW_WAVES), LW_WAVES * LW_BYTES, (hipStream_t)stream, a, rows);
     return (int)hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// pf_lookup_feat_kernel: the DCCL lookups of alternate_corr (pf_dccl_lookup_feat; statement: pf_lookup_feat_elem, pf_elem.h).
+// No volume exists: every bilinear corner is a C-long dot product <f1[n], P_i(f2)[p]> / sqrt(C).  One workgroup owns a tile of
+// LF_TY x LF_TX neighbouring pixels of one image at one level, one wave per pixel, and per view (own, then cross):
+//   P1  a lane per tap (81): the tap's PfTaps2 (the cross view through the level-0 grid) -> 4 corner element indices + weights;
+//   P2  dedup: the 81 taps of a view sample a 9 x 9 lattice, so corner (r0, *) of tap (a, b) is corner (r1, *) of tap (a, b-1)
+//       and corner (*, x0) of tap (a, b) is corner (*, x1) of tap (a-1, b) whenever their element indices agree; a ballot
+//       compacts the distinct corners (100 of 324 for the own view); the wave reduces their bounding box, then the workgroup;
+//   P3  TILE PATH, when the tile's box holds at most LF_CAP rows (smooth flow; the own view's box of a 2 x 4 tile is 11 x 13):
+//       the window rows of P_i(f2) are staged in LDS LF_CH channels at a time, ONE global read per row for the whole tile
+//       (instead of one per pixel and corner), and a lane per distinct corner accumulates its dot product from LDS with f1[n]
+//       broadcast; PIXEL PATH otherwise (seam, poles, large or scattered flow): each wave computes its distinct corners LF_G at a
+//       time from global memory, a lane holding 4 (8) channels of f1[n], a coalesced 1 KB row load, a butterfly over the wave;
+//   P4  a lane per tap: follows each corner to its computed dot and applies the weights in pf_apply_pairs' order.
+// The decision is made on the device per (tile, level, view) and is uniform over the workgroup; path_counts (optional) counts the
+// (tile, level, view) units that took each path.  Arithmetic: exact fp32 products (FMA) in every precision.  Tiles never span two
+// images, so results do not depend on B; the two paths sum the channels in different orders (rounding only).
+namespace {
+
+constexpr int LF_TY = 2, LF_TX = 4, LF_WAVES = LF_TY * LF_TX;   // pixel tile per workgroup (one wave per pixel)
+constexpr int LF_G = 8;                           // pixel path: dot products in flight per wave
+constexpr int LF_CH = 32;                         // tile path: channels per staged chunk
+constexpr int LF_LDW = LF_CH + 4;                 // tile path: LDS row stride (floats)
+constexpr int LF_CAP = 192;                       // tile path: window rows
+constexpr int LF_SLOTS = (4 * PF_TAPS + 63) / 64; // tile path: distinct corners per lane
+struct LfWave { int eidx[4 * PF_TAPS]; float wgt[4 * PF_TAPS]; int code[4 * PF_TAPS]; int uniq[4 * PF_TAPS]; float val[4 * PF_TAPS]; };
+
+__device__ __forceinline__ void lf_wave_sync() {   // lane -> lane hand-over through wave-private LDS (see pf_lookup_win_kernel)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ float lf_dot4(const float4 x, const float* p, float v) {
+    const float4 y = *reinterpret_cast<const float4*>(p);
+    v = fmaf(x.x, y.x, v); v = fmaf(x.y, y.y, v); v = fmaf(x.z, y.z, v); v = fmaf(x.w, y.w, v);
+    return v;
+}
+__device__ __forceinline__ int lf_wave_min(int v) { for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m)); return v; }
+__device__ __forceinline__ int lf_wave_max(int v) { for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m)); return v; }
+
+__global__ void __launch_bounds__(64 * LF_WAVES) pf_lookup_feat_kernel(const PfLookupFeatArgs a, const int tiles_y, const int tiles_x) {
+    __shared__ LfWave lf_smem[LF_WAVES];
+    __shared__ __attribute__((aligned(16))) float lf_win[LF_CAP * LF_LDW];
+    __shared__ int lf_box[LF_WAVES][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lvl = blockIdx.y;
+    const long tile = blockIdx.x;
+    const long b = tile / ((long)tiles_y * tiles_x);
+    const int t = (int)(tile % ((long)tiles_y * tiles_x));
+    const int py = (t / tiles_x) * LF_TY + wave / LF_TX, px = (t % tiles_x) * LF_TX + wave % LF_TX;
+    const bool live = py < a.H && px < a.W;          // partial tiles: dead waves keep to the barriers and write nothing
+    LfWave& s = lf_smem[wave];
+    const long N = (long)a.H * a.W;
+    const long n = live ? (long)py * a.W + px : 0;
+    const long row = b * N + n;
+    const int Wl = a.W >> lvl;
+    const long lsz = (long)(a.H >> lvl) * Wl;
+    const int c0 = 4 * lane, c1 = 256 + 4 * lane;                     // pixel path: this lane's channels (C <= 512, C % 4 == 0)
+    const bool h0 = c0 < a.C, h1 = c1 < a.C;
+    for (int view = 0; view < 2; ++view) {
+        __syncthreads();                                              // P4 / P3 of the previous view have read the LDS arrays
+        // ---- P1: taps -> corners ----------------------------------------------------------------------------------------
+        for (int tap = lane; tap < PF_TAPS; tap += 64) {
+            int e[4] = {-1, -1, -1, -1};
+            float w[4] = {0.f, 0.f, 0.f, 0.f};
+            if (live) {
+                const PfTaps2 tp = pf_lookup_feat_tap(a, b, n, lvl, tap, view != 0);
+                pf_taps2_corners(tp, e);
+                for (int j = 0; j < 4; ++j) w[j] = tp.w[j];
+            }
+            for (int j = 0; j < 4; ++j) { s.eidx[4 * tap + j] = e[j]; s.wgt[4 * tap + j] = w[j]; }
+        }
+        lf_wave_sync();
+        // ---- P2: dedup against the lattice neighbours, compact the distinct corners, their bounding box ------------------
+        int nu = 0, ymin = 1 << 30, ymax = -1, xmin = 1 << 30, xmax = -1;
+        for (int e0 = 0; e0 < 4 * PF_TAPS; e0 += 64) {
+            const int e = e0 + lane;
+            int code = -1;                                            // -1: weight 0; >= 0: slot; <= -2: same dot as entry -code-2
+            bool fresh = false;
+            if (e < 4 * PF_TAPS) {
+                const int idx = s.eidx[e];
+                if (idx >= 0) {
+                    const int tap = e >> 2, c = e & 3, ta = tap / 9, tb = tap % 9;
+                    if (tb > 0 && c < 2 && s.eidx[e - 2] == idx) code = -(e - 2) - 2;
+                    else if (ta > 0 && !(c & 1) && s.eidx[e - 35] == idx) code = -(e - 35) - 2;
+                    else fresh = true;
+                }
+            }
+            const unsigned long long m = __ballot(fresh);
+            if (fresh) {
+                const int idx = s.eidx[e];
+                code = nu + __popcll(m & ((1ull << lane) - 1ull));
+                s.uniq[code] = idx;
+                const int y = idx / Wl, x = idx - y * Wl;
+                ymin = min(ymin, y); ymax = max(ymax, y); xmin = min(xmin, x); xmax = max(xmax, x);
+            }
+            if (e < 4 * PF_TAPS) s.code[e] = code;
+            nu += __popcll(m);
+        }
+        ymin = lf_wave_min(ymin); ymax = lf_wave_max(ymax); xmin = lf_wave_min(xmin); xmax = lf_wave_max(xmax);
+        if (lane == 0) { lf_box[wave][0] = ymin; lf_box[wave][1] = ymax; lf_box[wave][2] = xmin; lf_box[wave][3] = xmax; }
+        __syncthreads();
+        int by0 = 1 << 30, by1 = -1, bx0 = 1 << 30, bx1 = -1;
+        for (int w = 0; w < LF_WAVES; ++w) {
+            by0 = min(by0, lf_box[w][0]); by1 = max(by1, lf_box[w][1]); bx0 = min(bx0, lf_box[w][2]); bx1 = max(bx1, lf_box[w][3]);
+        }
+        const int bw = bx1 - bx0 + 1;
+        const long nwin = by1 < by0 ? 0 : (long)(by1 - by0 + 1) * bw;   // 0: no corner with a weight in the whole tile
+        const bool tiled = nwin <= LF_CAP;                                // uniform over the workgroup
+        if (a.path_counts && threadIdx.x == 0) atomicAdd(a.path_counts + (tiled ? 0 : 1), 1);
+        // ---- P3: the distinct dot products ------------------------------------------------------------------------------
+        const float* f1 = (view ? a.f1_oth : a.f1_own) + row * a.C;
+        const float* f2 = (view ? a.f2_oth[lvl] : a.f2_own[lvl]) + b * lsz * a.C;
+        if (tiled) {
+            int ridx[LF_SLOTS];
+            float acc[LF_SLOTS];
+#pragma unroll
+            for (int j = 0; j < LF_SLOTS; ++j) {
+                const int u = lane + 64 * j;
+                int r = 0;
+                if (u < nu) { const int e = s.uniq[u]; const int y = e / Wl; r = (y - by0) * bw + (e - y * Wl - bx0); }
+                ridx[j] = r * LF_LDW;
+                acc[j] = 0.f;
+            }
+            for (int k0 = 0; k0 < a.C; k0 += LF_CH) {
+                const int kq = min(LF_CH, a.C - k0) / 4;                  // float4 pieces of this chunk (C % 4 == 0)
+                __syncthreads();                                          // the previous chunk has been read
+                for (long i = threadIdx.x; i < nwin * kq; i += 64 * LF_WAVES) {
+                    const int r = (int)(i / kq), q = (int)(i % kq);
+                    const int y = by0 + r / bw, x = bx0 + r % bw;
+                    *reinterpret_cast<float4*>(lf_win + r * LF_LDW + 4 * q) =
+                        *reinterpret_cast<const float4*>(f2 + ((long)y * Wl + x) * a.C + k0 + 4 * q);
+                }
+                __syncthreads();
+                for (int q = 0; q < kq; ++q) {
+                    const float4 x = *reinterpret_cast<const float4*>(f1 + k0 + 4 * q);     // same address in every lane
+#pragma unroll
+                    for (int j = 0; j < LF_SLOTS; ++j)
+                        if (lane + 64 * j < nu) acc[j] = lf_dot4(x, lf_win + ridx[j] + 4 * q, acc[j]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < LF_SLOTS; ++j)
+                if (lane + 64 * j < nu) s.val[lane + 64 * j] = acc[j] * a.scale;
+        } else {
+            const float4 z4 = {0.f, 0.f, 0.f, 0.f};
+            const float4 x0 = h0 ? *reinterpret_cast<const float4*>(f1 + c0) : z4;
+            const float4 x1 = h1 ? *reinterpret_cast<const float4*>(f1 + c1) : z4;
+            for (int u0 = 0; u0 < nu; u0 += LF_G) {
+                float acc[LF_G];
+#pragma unroll
+                for (int g = 0; g < LF_G; ++g) {
+                    const int u = u0 + g < nu ? u0 + g : u0;
+                    const float* r = f2 + (long)s.uniq[u] * a.C;
+                    float v = 0.f;
+                    if (h0) v = lf_dot4(x0, r + c0, v);
+                    if (h1) v = lf_dot4(x1, r + c1, v);
+                    acc[g] = v;
+                }
+#pragma unroll
+                for (int g = 0; g < LF_G; ++g)
+                    for (int m = 32; m >= 1; m >>= 1) acc[g] += __shfl_xor(acc[g], m);
+                if (lane == 0) {
+#pragma unroll
+                    for (int g = 0; g < LF_G; ++g)
+                        if (u0 + g < nu) s.val[u0 + g] = acc[g] * a.scale;
+                }
+            }
+        }
+        lf_wave_sync();
+        // ---- P4: bilinear weights ---------------------------------------------------------------------------------------
+        if (!live) continue;
+        float* out = (view ? a.raw_out : a.own_out) + row * a.ld + lvl * PF_TAPS;
+        for (int tap = lane; tap < PF_TAPS; tap += 64) {
+            float v[4];
+            for (int j = 0; j < 4; ++j) {
+                int e = 4 * tap + j, c = s.code[e];
+                while (c <= -2) { e = -c - 2; c = s.code[e]; }
+                v[j] = c >= 0 ? s.val[c] : 0.f;
+            }
+            const float* w = s.wgt + 4 * tap;
+            float acc = v[0] * w[0];
+            acc = acc + v[1] * w[1];
+            acc = acc + v[2] * w[2];
+            acc = acc + v[3] * w[3];
+            out[tap] = acc;
+        }
+    }
+}
+
+}  // namespace
+
+// Launcher behind PF_LOOKUP_FEAT_LAUNCH (pf_elem_kernels.hip); the entry point has validated the arguments.
+int pf_lookup_feat_launch(const PfLookupFeatArgs& a, void* stream) {
+    const int tiles_y = (a.H + LF_TY - 1) / LF_TY, tiles_x = (a.W + LF_TX - 1) / LF_TX;
+    const long blocks = (long)a.B * tiles_y * tiles_x;
+    if (blocks <= 0 || blocks >= (1L << 31) || (long)a.H * a.W >= (1L << 30)) return PF_ERR_BAD_SHAPE;
+    hipLaunchKernelGGL(pf_lookup_feat_kernel, dim3((unsigned)blocks, PF_CORR_LEVELS), dim3(64 * LF_WAVES), 0,
+                       (hipStream_t)stream, a, tiles_y, tiles_x);
+    return (int)hipGetLastError();
+}

@@ -328,14 +328,17 @@ def pack_update_blocks(oddc, upd, precision: Optional[int] = None) -> Dict[str, 
 class Workspace:
     """All device buffers of one (B, H, W) problem; allocated once, reused every call."""
 
-    def __init__(self, lib: PfLib, B: int, H: int, W: int, device, f16: bool = False):
+    def __init__(self, lib: PfLib, B: int, H: int, W: int, device, f16: bool = False, alt_corr: bool = False):
         """f16: the update blocks run in PREC_F16 -- their operand buffers (the ``*_s`` attributes) are f16 maps instead of split
-        twins; fnet's features for the corr build stay split twins."""
+        twins; fnet's features for the corr build stay split twins.
+        alt_corr: alternate_corr -- no correlation volumes: the pooled f2 levels 1-3 of both views (``feat_a`` / ``feat_b``,
+        level 0 is ``f["f2a"]`` / ``f["f2b"]``) instead of ``pyr_a`` / ``pyr_b``, and no bf16 twins of the features."""
         if H % 8 or W % 8 or H < 128 or W < 128:
             raise PfError(f"image size {H}x{W}: H and W must be multiples of 8 (callers pad, core/utils/utils.py:7-27) "
                           "and at least 128 (the coarsest pyramid level must be 2x2 or larger)")
         self.B, self.H, self.W = B, H, W
         self.f16 = f16
+        self.alt_corr = alt_corr
         self.H8, self.W8 = H // 8, W // 8
         self.N = self.H8 * self.W8
         self.device = device
@@ -359,12 +362,19 @@ class Workspace:
         # fnet output of the 4 images (f1A, f2A, f1B, f2B), one row block each
         self.f_all = z(4 * rows, 256)
         self.f = {k: self.f_all[i * rows:(i + 1) * rows] for i, k in enumerate(("f1a", "f2a", "f1b", "f2b"))}
-        self.f_split = torch.zeros(4 * rows, 8, 2, 32, dtype=torch.bfloat16, device=device)   # bf16 hi|lo rows
+        self.f_split = None if alt_corr else \
+            torch.zeros(4 * rows, 8, 2, 32, dtype=torch.bfloat16, device=device)              # bf16 hi|lo rows
         self.img_c = z(2 * B, 3, H, W)         # cnet input  [image1_A | image1_B]
         self.img_f = z(4 * B, 3, H, W)         # fnet input  [image1_A | image2_A | image1_B | image2_B]
         # ---- pyramids: level i rows [B*N, (H8>>i)*(W8>>i)]
-        self.pyr_a = [z(rows, (H8 >> i) * (W8 >> i)) for i in range(4)]
-        self.pyr_b = [z(rows, (H8 >> i) * (W8 >> i)) for i in range(4)]
+        # (alt_corr: B*N^2*4*1.33 bytes per view -> pooled features [B*N_i, 256], i = 1..3: B*N*256*4*0.33 bytes per view)
+        if alt_corr:
+            self.pyr_a = self.pyr_b = None
+            self.feat_a = [z(B * (H8 >> i) * (W8 >> i), 256) for i in (1, 2, 3)]
+            self.feat_b = [z(B * (H8 >> i) * (W8 >> i), 256) for i in (1, 2, 3)]
+        else:
+            self.pyr_a = [z(rows, (H8 >> i) * (W8 >> i)) for i in range(4)]
+            self.pyr_b = [z(rows, (H8 >> i) * (W8 >> i)) for i in range(4)]
         # ---- loop state
         # coords0 (the pixel grid, core/utils/utils.py:75-78) is a constant of the shape: built once, copied per forward
         xs = torch.arange(W8, device=device, dtype=torch.float32).view(1, 1, 1, W8).expand(B, 1, H8, W8)
@@ -505,7 +515,12 @@ class Engine:
 
     # ---- stage 1: corr volumes + pyramids (the encoders write the channel-last features themselves) ----------
     def build_pyramids(self, ws: Workspace, precision: int = PREC_F32):
-        """corr + build_pyramid for both views (core/prior_raft.py:151-159)."""
+        """corr + build_pyramid for both views (core/prior_raft.py:151-159); alternate_corr: pool the features instead
+        (AlternateCorrBlock, core/corr.py:64-74), in fp32 whatever the precision."""
+        if ws.alt_corr:
+            self.lib.feature_pyramid(ws.f["f2a"], ws.feat_a, ws.B, ws.H8, ws.W8)
+            self.lib.feature_pyramid(ws.f["f2b"], ws.feat_b, ws.B, ws.H8, ws.W8)
+            return
         if precision == PREC_BF16X3:
             if not getattr(ws, "f_split_ready", False):        # (round 6: fnet's last convolution writes the hi|lo rows itself)
                 self.lib.split_bf16(ws.f_all, ws.f_split)      # all four feature maps at once
@@ -518,6 +533,19 @@ class Engine:
             return
         self.lib.corr_pyramid(ws.f["f1a"], ws.f["f2a"], ws.pyr_a, ws.B, ws.H8, ws.W8)
         self.lib.corr_pyramid(ws.f["f1b"], ws.f["f2b"], ws.pyr_b, ws.B, ws.H8, ws.W8)
+
+    def lookup(self, ws: Workspace, branch: str, own_out: torch.Tensor, raw_out: torch.Tensor):
+        """DCCL lookups of one branch (core/corr.py:113-137): own view in the branch's pyramid, raw cross view in the other
+        branch's at the grid into it (A: grid(R_B2A), B: grid(R_A2B)).  The one place the two correlation modes meet:
+        pf_dccl_lookup on the volumes, or pf_dccl_lookup_feat on the pooled features (alternate_corr)."""
+        own, oth = ("a", "b") if branch == "a" else ("b", "a")
+        coords = ws.c1a if branch == "a" else ws.c1b
+        g, g_il = (ws.g_b2a_8, ws.g_b2a_8_il) if branch == "a" else (ws.g_a2b_8, ws.g_a2b_8_il)
+        if ws.alt_corr:
+            levels = lambda t: [ws.f["f2" + t]] + getattr(ws, "feat_" + t)  # noqa: E731
+            self.lib.dccl_lookup_feat(coords, ws.f["f1" + own], levels(own), ws.f["f1" + oth], levels(oth), g, own_out, raw_out)
+        else:
+            self.lib.dccl_lookup(coords, getattr(ws, "pyr_" + own), getattr(ws, "pyr_" + oth), g, own_out, raw_out, g_il)
 
     def init_coords(self, ws: Workspace, init_flow: Optional[torch.Tensor]):
         """initialize_flow (+ init_flow) (core/prior_raft.py:161-165)."""
@@ -581,14 +609,14 @@ class Engine:
         start = torch.cuda.Event()
         start.record(main)
         # ---- heads: lookup, rotate-back + add + convc1, convc2 (no dependence on the flow chain)
-        lib.dccl_lookup(ws.c1a, ws.pyr_a, ws.pyr_b, ws.g_b2a_8, ws.own, ws.raw, ws.g_b2a_8_il)
+        self.lookup(ws, "a", ws.own, ws.raw)
         lib.dccl_combine_conv1x1([(ws.own, ws.raw, ws.g_b2a_8, P["a.c1"], None, 0, ws.c1_a_s)], B, H8, W8)
         conv(P["a.c2"].desc(None, 0, 256, None, 0, EPI_RELU, in0s=ws.c1_a_s, outs=ws.cat_a_s))
         b_prev = self._b_pending                # end of B's previous chain: the flow chain reads its coords1
         if need_b:
             sb.wait_event(start)
             with torch.cuda.stream(sb):
-                lib.dccl_lookup(ws.c1b, ws.pyr_b, ws.pyr_a, ws.g_a2b_8, ws.own_b, ws.raw_b, ws.g_a2b_8_il)
+                self.lookup(ws, "b", ws.own_b, ws.raw_b)
                 lib.dccl_combine_conv1x1([(ws.own_b, ws.raw_b, ws.g_a2b_8, P["b.c1"], None, 0, ws.c1_b_s)], B, H8, W8)
                 conv(P["b.c2"].desc(None, 0, 256, None, 0, EPI_RELU, in0s=ws.c1_b_s, outs=ws.cat_b_s))
         # ---- flow chain (s1) and confidence chain (s2): need both branches' coords1
@@ -728,12 +756,12 @@ class Engine:
         ps = self.presplit(P)
 
         def look_a():
-            lib.dccl_lookup(ws.c1a, ws.pyr_a, ws.pyr_b, ws.g_b2a_8, ws.own, ws.raw, ws.g_b2a_8_il)
+            self.lookup(ws, "a", ws.own, ws.raw)
             if not fused:
                 lib.dccl_combine(ws.own, ws.raw, ws.g_b2a_8, ws.corr_a, B, H8, W8)
 
         def look_b():
-            lib.dccl_lookup(ws.c1b, ws.pyr_b, ws.pyr_a, ws.g_a2b_8, ws.own_b, ws.raw_b, ws.g_a2b_8_il)
+            self.lookup(ws, "b", ws.own_b, ws.raw_b)
             if not fused:
                 lib.dccl_combine(ws.own_b, ws.raw_b, ws.g_a2b_8, ws.corr_b, B, H8, W8)
 
@@ -795,10 +823,10 @@ class Engine:
         """flows, flo_rotate and the DCCL lookups of one iteration, single stream (tests)."""
         lib, B, H8, W8 = self.lib, ws.B, ws.H8, ws.W8
         self._flow_chain_head(ws)
-        lib.dccl_lookup(ws.c1a, ws.pyr_a, ws.pyr_b, ws.g_b2a_8, ws.own, ws.raw, ws.g_b2a_8_il)
+        self.lookup(ws, "a", ws.own, ws.raw)
         lib.dccl_combine(ws.own, ws.raw, ws.g_b2a_8, ws.corr_a, B, H8, W8)
         if need_b:
-            lib.dccl_lookup(ws.c1b, ws.pyr_b, ws.pyr_a, ws.g_a2b_8, ws.own, ws.raw, ws.g_a2b_8_il)
+            self.lookup(ws, "b", ws.own, ws.raw)
             lib.dccl_combine(ws.own, ws.raw, ws.g_a2b_8, ws.corr_b, B, H8, W8)
 
     def motion_inputs(self, ws: Workspace, P, need_b: bool):

@@ -35,7 +35,14 @@ class PriOr_RAFT(nn.Module):
     confidence stems and flow_head.conv2 fp32.  The encoders and the corr build keep bf16x3 (the reference's autocast over the
     encoders, :133, is not followed; the correlation is fp32 there, :146-153).  The training forward (``train()`` with autograd)
     keeps its bf16x3 arithmetic whatever the flag says: fp16 training with loss scaling (train_flow.py:112,136-139) is not
-    implemented.  ``args.dropout`` is honoured by the training forward."""
+    implemented.  ``args.dropout`` is honoured by the training forward.
+
+    ``args.alternate_corr=True`` (or ``model.alternate_corr = True``; None follows args) selects RAFT's alternate correlation
+    for the inference forward, eager and graph replay, any batch, with every precision: no all-pairs volume and no pyramid of
+    it (B*N^2*4*1.33 bytes per view, N = H/8 * W/8: 141 GB for both views at 1920x3840) -- f2 is pooled instead (levels 1-3,
+    2x2 floor means, B*N*256*4*0.33 bytes per view) and each lookup computes its bilinear corners as fp32 dot products
+    <f1[n], P_i(f2)[p]> / sqrt(C), which equal the volume's entries up to rounding because pooling is linear.  The lookups
+    cost more time than reading the volumes.  The training forward refuses the flag (PfError)."""
 
     def __init__(self, args):
         super().__init__()
@@ -55,6 +62,7 @@ class PriOr_RAFT(nn.Module):
         self._enc_sig = None
         self.use_graph = os.environ.get("PRIORFLOW_GRAPH", "1") != "0"
         self.precision: Optional[int] = None      # None -> args.mixed_precision (PREC_F16), else PRIORFLOW_PRECISION (default bf16x3)
+        self.alternate_corr: Optional[bool] = None   # None -> args.alternate_corr
         self.use_streams = os.environ.get("PRIORFLOW_STREAMS", "1") != "0"
         self._side_streams = None
 
@@ -93,6 +101,12 @@ class PriOr_RAFT(nn.Module):
             return self.precision
         return _lib.PREC_F16 if getattr(self.args, "mixed_precision", False) else None
 
+    def _alt_corr(self) -> bool:
+        """Correlation without volumes (AlternateCorrBlock): ``model.alternate_corr`` when set, else ``args.alternate_corr``."""
+        if self.alternate_corr is not None:
+            return bool(self.alternate_corr)
+        return bool(getattr(self.args, "alternate_corr", False))
+
     def _weights(self):
         params = list(self.ODDC.parameters()) + list(self.update_block.parameters())
         pr = self._update_precision()
@@ -112,15 +126,17 @@ class PriOr_RAFT(nn.Module):
         HIP graphs captured on them: an evaluation loop over mixed sizes (or B = 1 / B = 32 in turn) re-uses its workspaces and
         graphs instead of re-allocating ~1 GB and re-capturing 258 kernels per switch."""
         f16 = self._weights()["precision"] == _lib.PREC_F16          # the update blocks' operands as f16 maps
+        alt = self._alt_corr()
         key = (B, H, W, str(device))
         ws = self._ws.pop(key, None)
-        if ws is not None and ws.f16 != f16:
-            # mixed_precision was switched: the operand buffers of the update blocks change form (twins <-> f16 maps)
+        if ws is not None and (ws.f16 != f16 or ws.alt_corr != alt):
+            # mixed_precision was switched: the operand buffers of the update blocks change form (twins <-> f16 maps);
+            # alternate_corr was switched: pyramids <-> pooled features
             for gk in [gk for gk in self._graphs if (gk[0], gk[1], gk[2], gk[4]) == key]:
                 del self._graphs[gk]
             ws = None
         if ws is None:
-            ws = Workspace(self._lib(), B, H, W, device, f16=f16)
+            ws = Workspace(self._lib(), B, H, W, device, f16=f16, alt_corr=alt)
             ws.nbytes = sum(t.numel() * t.element_size() for t in vars(ws).values() if isinstance(t, torch.Tensor)) + \
                 sum(t.numel() * t.element_size() for v in vars(ws).values() if isinstance(v, (list, tuple))
                     for t in v if isinstance(t, torch.Tensor))
@@ -177,7 +193,7 @@ class PriOr_RAFT(nn.Module):
         # separate split launch (21-37 us of kernel time between the encoders and the corr build) is gone (round 6; the forward's
         # wall time did not move: 147.1 against 147.2 pairs/s, profiles/r6_ab_head.txt -- the stretch overlaps cnet's tail)
         from ._lib import PREC_BF16X3
-        fsplit = dict(outs=ws.f_split) if Engine.encoder_precision(self._weights()) == PREC_BF16X3 and fplan.precision == PREC_BF16X3 else {}
+        fsplit = dict(outs=ws.f_split) if ws.f_split is not None and Engine.encoder_precision(self._weights()) == PREC_BF16X3 and fplan.precision == PREC_BF16X3 else {}
         ws.f_split_ready = bool(fsplit)
         P = self._weights()
         if self.use_streams and int(os.environ.get("PRIORFLOW_FORKS", "15")) & 1:
@@ -255,6 +271,9 @@ class PriOr_RAFT(nn.Module):
                                "there is no CPU fallback (the CPU restatement lives in oracle/ and is test-only)")
         if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
             # training caller (train_flow.py:131): autograd tape over the HIP forward / backward kernels
+            if self._alt_corr():
+                raise _lib.PfError("alternate_corr is inference-only: the training forward keeps its correlation volumes "
+                                   "(set model.alternate_corr = False or args.alternate_corr = False to train)")
             from .autograd import train_forward
             with torch.cuda.device(image1.device):
                 preds_a, preds_b = train_forward(self, image1, image2, iters, init_flow)
@@ -282,6 +301,7 @@ class PriOr_RAFT(nn.Module):
         # the captured launches hold pointers to PACKED copies of the weights, of the encoders' too
         self._weights()
         self._encoder_plans()
+        # (no mode in the key: _workspace drops a shape's graphs whenever its workspace changes mode -- mixed_precision, alternate_corr)
         key = (ws.B, ws.H, ws.W, iters, str(image1.device))
         # The input stage (pf_prepare_images: normalise + rotate into the encoders' batches) runs OUTSIDE the graph, straight from the
         # caller's tensors into the workspace, and the capture starts behind it: a replay needs no copy of the images into static
