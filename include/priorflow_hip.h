@@ -331,21 +331,28 @@ int pf_dccl_combine_conv1x1_f16(const pf_combine_conv_desc* descs, int ngroups, 
  * branch A and branch B of an iteration run side by side.  H8, W8 = OUTPUT map size. */
 int pf_conv2d(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8, void* stream);
 
-/* Host-only introspection: which workgroup tile pf_conv2d would use for this launch -- generic kernel 0: 128x32,
- * 1: 64x64, 2: 64x128, 7: 128x96 (pixels x channels; 7 = round 6, for the 96 output channels of the encoders' layer 2); halo kernel 3: 128x64, 4: 128x128, 5: 256x64 (8-row tile), 8: 256x96 (8-row tile, 3x3 with 64 < Cout <= 96; round 6); 6: the
- * weights-stationary kernel of the encoders' 3x3 64 -> 64 convolutions (round 5; core/extractor.py:16-17 at 1/2 resolution:
- * strips of 32 columns walked in 4-row steps, outputs bit-identical to tile 5) -- or a negative PF_ERR_* code.  Lets a profiler attribute measured time to the right kernel instantiation; launches nothing. */
+/* Host-only queries: pf_conv2d plans every launch once (validation, tile, kernel instantiation, wave organisation, statistics
+ * blocks) and runs that plan; each query computes the same plan and returns one field of it, or the negative PF_ERR_* code with
+ * which pf_conv2d refuses the descriptors.  They launch nothing and need no GPU.
+ *
+ * pf_conv2d_tile: the workgroup tile of the launch -- generic kernel 0: 128x32, 1: 64x64, 2: 64x128, 7: 128x96 (pixels x
+ * channels; 7 = round 6, for the 96 output channels of the encoders' layer 2); halo kernel 3: 128x64, 4: 128x128, 5: 256x64
+ * (8-row tile), 8: 256x96 (8-row tile, 3x3 with 64 < Cout <= 96; round 6); 6: the weights-stationary kernel of the encoders'
+ * 3x3 64 -> 64 convolutions (round 5; core/extractor.py:16-17 at 1/2 resolution: strips of 32 columns walked in 4-row steps,
+ * outputs bit-identical to tile 5).  Lets a profiler attribute measured time to the right kernel instantiation. */
 int pf_conv2d_tile(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8);
 
-/* Host-only introspection: how many fp64 partial blocks PER IMAGE this launch writes to `stats_out` (the nblk of
- * pf_channel_stats_final and of the buffer's size, [B][nblk][cout][2] doubles); 0 = this launch cannot fuse the statistics
- * (generic kernel whose pixel tiles would straddle images, or not bf16x3); negative = PF_ERR_*.  Launches nothing. */
+/* pf_conv2d_stats_blocks: how many fp64 partial blocks PER IMAGE the launch writes to `stats_out` (the nblk of
+ * pf_channel_stats_final and of the buffer's size, [B][nblk][cout][2] doubles), answered for the launch with `stats_out` set;
+ * 0 = the launch cannot fuse the statistics (generic kernel whose pixel tiles would straddle images, or not bf16x3). */
 int pf_conv2d_stats_blocks(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8);
 
-/* Host-only introspection, companion of pf_conv2d_tile for tiles 3 / 4: which wave organisation the launch takes --
+/* pf_conv2d_roles: the wave organisation of the launch.  Nonzero only with tiles 3, 4, 5 and 8; 0 on every other tile
+ * (the generic kernel, the weights-stationary kernel 6) --
  * 0: every wave stages and multiplies (pf_conv_halo_kernel), 1: four MFMA waves + four loader waves on the same tile
- * (pf_conv_ws_kernel<NT, KH, KW, 2>), 2: the same with a 256 px x 64 channel tile (pf_conv_ws_kernel<2, KH, KW, 1>);
- * 16 + 1 | 16 + 2: the launch has pre-split operands and takes the all-DMA kernel (pf_conv_dma_kernel) with that tile. */
+ * (pf_conv_ws_kernel<NT, KH, KW, 2>; tiles 3 / 4), 2: the same with a 256 px x 64 channel tile (pf_conv_ws_kernel<2, KH, KW, 1>;
+ * tiles 3 / 4); 16 + 1 | 16 + 2: the launch has pre-split operands and takes the all-DMA kernel (pf_conv_dma_kernel) with
+ * that tile (tiles 3, 4, 5, 8; tile 5 always with 16 + 2). */
 int pf_conv2d_roles(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8);
 
 /* The encoders' first convolution (core/extractor.py:122, :144: conv1 7x7 stride 2 pad 3, 3 -> 64) straight from the NCHW

@@ -1,11 +1,12 @@
-// pf_conv2d: argument validation, tile choice and dispatch (host side).  The kernels live in pf_conv_mfma.hip (generic,
-// halo and role-specialised kernels on fp32 activations) and pf_conv_dma.hip (all-DMA kernel on pre-split activations).
+// pf_conv2d: the launch plan (validation, tile, kernel instantiation, roles, statistics blocks) and its dispatch, host side.
+// The kernels live in pf_conv_mfma.hip (generic, halo and role-specialised kernels on fp32 activations), pf_enc_conv.hip
+// (weights-stationary kernel) and pf_conv_dma.hip (all-DMA kernel on pre-split activations).
 #include <stdlib.h>
 #include "pf_conv_priv.h"
 
 using namespace pfconv;
 
-// validation + geometry shared by pf_conv2d and pf_conv2d_tile
+// validation of the descriptors + geometry (conv_plan)
 static int conv_prepare(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8,
                         ConvGroups& grp, ConvGeom& g, int& max_cout) {   // H8, W8: OUTPUT map size
     if (!descs || ngroups < 1 || ngroups > MAX_GROUPS) return PF_ERR_BAD_ARG;
@@ -102,16 +103,20 @@ static int conv_tile(const ConvGeom& g, int ngroups, int max_cout, int precision
     return 2;
 }
 
+// The shapes and options of the all-DMA and the role-specialised kernels: 3x3, 1x5, 5x1 stride 1, no input affine, no fused statistics
+static bool roles_apply(const ConvGroups& grp, int ngroups, const ConvGeom& g) {
+    if (!((g.kh == 3 && g.kw == 3) || (g.kh == 1 && g.kw == 5) || (g.kh == 5 && g.kw == 1)) || g.stride != 1) return false;
+    for (int i = 0; i < ngroups; ++i)
+        if (grp.d[i].stats_out != nullptr || grp.d[i].in_scale != nullptr) return false;
+    return true;
+}
+
 // Pre-split operands (pf_conv_desc.in0_split): which tile the all-DMA kernel takes -- 0: not applicable (fp32 operands,
 // a shape / option it does not implement), else the pf_conv2d_roles code (1: 128-px tile, 2: 256 px x 64 channels).
 // (The engine's PRIORFLOW_PRESPLIT=0 is the A/B against the register-staged kernels: it hands over fp32 operands.)
-// PF_PREC_F16 exists on this kernel only: a launch it does not take is an error for the caller (f16_plan), never a fallback.
+// PF_PREC_F16 exists on this kernel only: a launch it does not take is an error for the caller (conv_plan), never a fallback.
 static int conv_dma_choice(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout, int tile_id) {
-    if (!grp.d[0].in0_split || tile_id < 3 || tile_id == 7) return 0;
-    const bool shape = (g.kh == 3 && g.kw == 3) || (g.kh == 1 && g.kw == 5) || (g.kh == 5 && g.kw == 1);
-    if (!shape || g.stride != 1) return 0;
-    for (int i = 0; i < ngroups; ++i)
-        if (grp.d[i].stats_out != nullptr || grp.d[i].in_scale != nullptr) return 0;
+    if (!grp.d[0].in0_split || tile_id < 3 || tile_id == 7 || !roles_apply(grp, ngroups, g)) return 0;
     if (tile_id == 5) return 2;            // Cout <= 64 on a big map (3x3 by conv_tile's rule): the 256 px x 64 channel tile
     const long wgs256 = (long)(g.M / g.N) * ((g.H + 7) / 8) * ((g.W + 31) / 32) * (ngroups + grp.d[0].co_groups) * ((max_cout + 63) / 64);
     // round 4: the 256 px x 64 channel tile for the 1x5 / 5x1 convolutions with Cout > 128 (the GRU's fused z|r) too: half the
@@ -120,74 +125,97 @@ static int conv_dma_choice(const ConvGroups& grp, int ngroups, const ConvGeom& g
     return (g.kh == 3 && max_cout > 64 && wgs256 >= 256) ? 2 : 1;
 }
 
-
-// PF_PREC_F16 launch: PF_OK when the all-DMA kernel takes it, PF_ERR_BAD_SHAPE otherwise (any other precision: PF_OK)
-static int f16_plan(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout, int tile) {
-    if (grp.d[0].precision != PF_PREC_F16) return PF_OK;
-    return conv_dma_choice(grp, ngroups, g, max_cout, tile) ? PF_OK : PF_ERR_BAD_SHAPE;
+// Which form of the halo kernel a TH = 4 launch takes: 0 the symmetric pf_conv_halo_kernel, 1 pf_conv_ws_kernel with the
+// call's own 128-px tile (WN = 2), 2 pf_conv_ws_kernel with the 256 px x 64 channel tile (WN = 1; only where that still
+// gives every CU a workgroup).  PRIORFLOW_CONV_WS (A/B knob): 0 / 1 cap the choice, default 2.
+static int conv_ws_choice(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout) {
+    static const int ws = [] { const char* e = getenv("PRIORFLOW_CONV_WS"); return e ? atoi(e) : 2; }();
+    if (ws <= 0 || !roles_apply(grp, ngroups, g)) return 0;
+    const long wgs256 = (long)(g.M / g.N) * ((g.H + 7) / 8) * ((g.W + 31) / 32) * ngroups * ((max_cout + 63) / 64);
+    // (measured: the 256-px tile wins for the 3x3 convs, -2 % at B=1; for 1x5 / 5x1 its taller halo costs more than the weights save)
+    if (ws >= 3 && g.kh == 3 && wgs256 >= 256) return 2;       // A/B: the 256 px x 64 channel roles kernel for Cout <= 64 as well
+    return (ws >= 2 && g.kh == 3 && max_cout > 64 && wgs256 >= 256) ? 2 : 1;
 }
 
-extern "C" int pf_conv2d_tile(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8) {
-    ConvGroups grp; ConvGeom g; int max_cout;
-    const int rc = conv_prepare(descs, ngroups, B, H8, W8, grp, g, max_cout);
-    if (rc != PF_OK) return rc;
-    const int tile = conv_tile(g, ngroups + descs[0].co_groups, max_cout, descs[0].precision);
-    if (const int e = f16_plan(grp, ngroups, g, max_cout, tile)) return e;
-    // 6: the weights-stationary kernel of the encoders' 3x3 64 -> 64 convolutions (pf_enc_conv.hip): its statistics partials are
-    // per (segment, row phase, strip) -- pf_conv2d_stats_blocks
-    return ((tile == 5 || tile == 3) && pf_enc_conv64_applies(grp, ngroups, g, max_cout)) ? 6 : tile;
-}
-
-extern "C" int pf_conv2d_stats_blocks(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8) {
-    ConvGroups grp; ConvGeom g; int max_cout;
-    const int rc = conv_prepare(descs, ngroups, B, H8, W8, grp, g, max_cout);
-    if (rc != PF_OK) return rc;
-    const int tile = conv_tile(g, ngroups + descs[0].co_groups, max_cout, descs[0].precision);
-    if (const int e = f16_plan(grp, ngroups, g, max_cout, tile)) return e;
+// The plan of one launch: PF_OK, or the PF_ERR_* code with which pf_conv2d refuses the descriptors.  Every decision about a
+// pf_conv2d launch is made here, once; pf_conv2d runs p.launch and the three queries read one field each.
+static int conv_plan(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8, ConvPlan& p) {
+    if (const int rc = conv_prepare(descs, ngroups, B, H8, W8, p.grp, p.g, p.max_cout)) return rc;
+    const ConvGroups& grp = p.grp;
+    const ConvGeom& g = p.g;
+    p.ngroups = ngroups;
+    p.tile = conv_tile(g, ngroups + descs[0].co_groups, p.max_cout, descs[0].precision);
+    const int dma = conv_dma_choice(grp, ngroups, g, p.max_cout, p.tile);
+    if (descs[0].precision == PF_PREC_F16 && !dma) return PF_ERR_BAD_SHAPE;     // f16 operands exist on the all-DMA kernel only
     const bool split = descs[0].precision == PF_PREC_BF16X3;
-    if ((tile == 5 || tile == 3) && pf_enc_conv64_applies(grp, ngroups, g, max_cout)) return pf_enc_conv64_stats_blocks(g);
-    if (tile >= 3 && tile != 7) { const int th = (tile == 5 || tile == 8) ? 8 : 4; return ((g.H + th - 1) / th) * ((g.W + 31) / 32); }
-    const int bm = (tile == 0 || tile == 7) ? 128 : 64;  // generic kernel: tiles of bm consecutive pixels, which must not straddle images
-    return (split && g.N % bm == 0) ? g.N / bm : 0;
-}
-
-extern "C" int pf_conv2d_roles(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8) {
-    ConvGroups grp; ConvGeom g; int max_cout;
-    const int rc = conv_prepare(descs, ngroups, B, H8, W8, grp, g, max_cout);
-    if (rc != PF_OK) return rc;
-    const int tile = conv_tile(g, ngroups + descs[0].co_groups, max_cout, descs[0].precision);
-    if (const int e = f16_plan(grp, ngroups, g, max_cout, tile)) return e;
-    if (const int dma = conv_dma_choice(grp, ngroups, g, max_cout, tile)) return 16 + dma;
-    return (tile == 3 || tile == 4) ? pf_conv_ws_choice(grp, ngroups, g, max_cout) : 0;
-}
-
-extern "C" int pf_conv2d(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8, void* stream) {
-    ConvGroups grp; ConvGeom g; int max_cout;
-    const int rc = conv_prepare(descs, ngroups, B, H8, W8, grp, g, max_cout);
-    if (rc != PF_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const bool split = descs[0].precision == PF_PREC_BF16X3;
-    const int tile_id = conv_tile(g, ngroups + descs[0].co_groups, max_cout, descs[0].precision);
-    if (const int e = f16_plan(grp, ngroups, g, max_cout, tile_id)) return e;
-    const bool generic = tile_id < 3 || tile_id == 7;
+    const bool generic = p.tile < 3 || p.tile == 7;
+    const int bm = (p.tile == 0 || p.tile == 7) ? 128 : 64;  // generic kernel: tiles of bm consecutive pixels, which must not straddle images
     for (int i = 0; i < ngroups; ++i) {     // the input affine is implemented by the halo kernel only; the fused statistics by the
         if (descs[i].in_scale && generic) return PF_ERR_BAD_SHAPE;          // halo kernel and (round 4) by the generic one when its
         if (descs[i].stats_out && descs[i].epilogue != PF_EPI_LINEAR) return PF_ERR_BAD_SHAPE;     // M tiles do not straddle images
-        if (descs[i].stats_out && generic && (!split || (g.N % ((tile_id == 0 || tile_id == 7) ? 128 : 64)) != 0)) return PF_ERR_BAD_SHAPE;
+        if (descs[i].stats_out && generic && (!split || g.N % bm != 0)) return PF_ERR_BAD_SHAPE;
     }
-    if (const int roles = conv_dma_choice(grp, ngroups, g, max_cout, tile_id))      // pre-split operands: the all-DMA kernel
-        return pf_conv_dma_launch(grp, ngroups, g, max_cout, tile_id == 4 ? 2 : 1, roles, s);
+    // tile 5 (Cout <= 64 on a big map) with 64 input channels: the weights-stationary kernel, bit-identical to the halo kernel
+    const bool enc64 = (p.tile == 5 || p.tile == 3) && pf_enc_conv64_applies(grp, ngroups, g, p.max_cout);
+    // statistics partials per image of the launch with stats_out (which never takes the all-DMA kernel): the weights-stationary
+    // kernel's per (segment, row phase, strip), the halo kernels' per pixel tile, the generic kernel's per bm pixels
+    const int th = (p.tile == 5 || p.tile == 8) ? 8 : 4;
+    p.stats_blocks = enc64 ? pf_enc_conv64_stats_blocks(g)
+                   : generic ? ((split && g.N % bm == 0) ? g.N / bm : 0) : ((g.H + th - 1) / th) * ((g.W + 31) / 32);
+    p.affine = false;
+    if (dma) {                              // pre-split operands: the all-DMA kernel, which reads its zero padding from memory
+        for (int i = 0; i < ngroups; ++i)
+            if (!descs[i].zeros || descs[i].zeros_bytes < 128 * (descs[i].lds0 > descs[i].lds1 ? descs[i].lds0 : descs[i].lds1)) return PF_ERR_BAD_ARG;
+        p.roles = 16 + dma;
+        p.launch = dma == 2 ? pf_conv_dma_launch<2, 1> : p.tile == 4 ? pf_conv_dma_launch<2, 2> : pf_conv_dma_launch<1, 2>;
+        return PF_OK;
+    }
     for (int i = 0; i < ngroups; ++i) {
         if (!descs[i].in0 || (descs[i].c1 > 0 && !descs[i].in1)) return PF_ERR_BAD_ARG;   // fp32 operands needed from here on
         if (descs[i].pre) return PF_ERR_BAD_SHAPE;                                          // accumulator start values: all-DMA kernel only
     }
-    // tile 5 (Cout <= 64 on a big map) with 64 input channels: the weights-stationary kernel, bit-identical to the halo kernel
-    if ((tile_id == 5 || tile_id == 3) && pf_enc_conv64_applies(grp, ngroups, g, max_cout)) return pf_enc_conv64_launch(grp, g, s);
-    switch (tile_id) {
-        case 0: case 1: case 2: case 7: return pf_conv_part0_launch(tile_id, grp, ngroups, g, max_cout, split, s);
-        case 3: return pf_conv_part1_launch(grp, ngroups, g, max_cout, s);
-        case 4: return pf_conv_part2_launch(grp, ngroups, g, max_cout, s);
-        case 8: return pf_conv_part4_launch(grp, ngroups, g, max_cout, s);
-        default: return pf_conv_part3_launch(grp, ngroups, g, max_cout, s);
+    p.roles = 0;
+    if (enc64) { p.tile = 6; p.launch = pf_enc_conv64_launch; return PF_OK; }
+    if (!generic) {                         // every group agrees on having an input affine (one instantiation per launch)
+        p.affine = descs[0].in_scale != nullptr;
+        for (int i = 1; i < ngroups; ++i)
+            if ((descs[i].in_scale != nullptr) != p.affine) return PF_ERR_BAD_ARG;
+        if (p.affine && (g.kh != 3 || g.kw != 3)) return PF_ERR_BAD_SHAPE;   // only the encoders' 3x3 convs use it
     }
+    if (p.tile == 3 || p.tile == 4) p.roles = conv_ws_choice(grp, ngroups, g, p.max_cout);
+    switch (p.tile) {
+        case 0: p.launch = pf_conv_generic_launch<4, 1, 1>; break;
+        case 1: p.launch = pf_conv_generic_launch<2, 2, 1>; break;
+        case 2: p.launch = pf_conv_generic_launch<2, 2, 2>; break;
+        case 7: p.launch = pf_conv_generic_launch<4, 1, 3>; break;
+        case 3: p.launch = p.roles == 2 ? pf_conv_ws_launch<2, 1> : p.roles == 1 ? pf_conv_ws_launch<1, 2> : pf_conv_halo_launch<1, 4>; break;
+        case 4: p.launch = p.roles == 2 ? pf_conv_ws_launch<2, 1> : p.roles == 1 ? pf_conv_ws_launch<2, 2> : pf_conv_halo_launch<2, 4>; break;
+        case 5: p.launch = pf_conv_halo_launch<2, 8>; break;
+        default: p.launch = pf_conv_halo_launch<3, 8>; break;     // 8
+    }
+    return PF_OK;
+}
+
+extern "C" int pf_conv2d_tile(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8) {
+    ConvPlan p;
+    const int rc = conv_plan(descs, ngroups, B, H8, W8, p);
+    return rc != PF_OK ? rc : p.tile;
+}
+
+extern "C" int pf_conv2d_stats_blocks(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8) {
+    ConvPlan p;
+    const int rc = conv_plan(descs, ngroups, B, H8, W8, p);
+    return rc != PF_OK ? rc : p.stats_blocks;
+}
+
+extern "C" int pf_conv2d_roles(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8) {
+    ConvPlan p;
+    const int rc = conv_plan(descs, ngroups, B, H8, W8, p);
+    return rc != PF_OK ? rc : p.roles;
+}
+
+extern "C" int pf_conv2d(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8, void* stream) {
+    ConvPlan p;
+    const int rc = conv_plan(descs, ngroups, B, H8, W8, p);
+    return rc != PF_OK ? rc : p.launch(p, (hipStream_t)stream);
 }

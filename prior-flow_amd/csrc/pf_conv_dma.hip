@@ -515,63 +515,50 @@ int launch_conv_dma_t(const ConvGroups& grp, int ngroups, const ConvGeom& g, int
 
 }  // namespace
 
-// One translation unit per kernel shape (PF_DMA_PART = 0..6, compiled in parallel by __graft_entry__.build_hip: an unrolled
-// K-step body takes about a minute per instantiation) plus the dispatcher (PF_DMA_PART = 7).  A unit holds both operand forms
-// of its shape (split twins and f16 maps).
-//   part: 0 <2,3,3,1>  1 <2,3,3,2>  2 <2,1,5,2>  3 <2,5,1,2>  4 <1,3,3,2>  5 <1,1,5,2>  6 <1,5,1,2>  8 <2,1,5,1>  9 <2,5,1,1>   (<NT, KH, KW, WN>)
+// One translation unit per kernel shape (PF_DMA_PART = 0..6, 8, 9, compiled in parallel by __graft_entry__.build_hip: an
+// unrolled K-step body takes about a minute per instantiation) plus the family launchers (PF_DMA_PART = 7).  A unit holds both
+// operand forms of its shape (split twins and f16 maps).
 #ifndef PF_DMA_PART
-#error "compile pf_conv_dma.hip with -DPF_DMA_PART=0..7"
+#error "compile pf_conv_dma.hip with -DPF_DMA_PART=0..9"
 #endif
-#define PF_DMA_DEFINE_PART(N, NT, KH, KW, WN)                                                                              \
-    int pf_conv_dma_part##N##_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout,   \
-                                     bool f16, hipStream_t stream) {                                                        \
-        return f16 ? launch_conv_dma_t<NT, KH, KW, WN, true>(grp, ngroups, g, max_cout, stream)                             \
-                   : launch_conv_dma_t<NT, KH, KW, WN, false>(grp, ngroups, g, max_cout, stream);                           \
-    }
-#if PF_DMA_PART == 0
-PF_DMA_DEFINE_PART(0, 2, 3, 3, 1)
-#elif PF_DMA_PART == 1
-PF_DMA_DEFINE_PART(1, 2, 3, 3, 2)
-#elif PF_DMA_PART == 2
-PF_DMA_DEFINE_PART(2, 2, 1, 5, 2)
-#elif PF_DMA_PART == 3
-PF_DMA_DEFINE_PART(3, 2, 5, 1, 2)
-#elif PF_DMA_PART == 4
-PF_DMA_DEFINE_PART(4, 1, 3, 3, 2)
-#elif PF_DMA_PART == 5
-PF_DMA_DEFINE_PART(5, 1, 1, 5, 2)
-#elif PF_DMA_PART == 6
-PF_DMA_DEFINE_PART(6, 1, 5, 1, 2)
-#elif PF_DMA_PART == 8
-PF_DMA_DEFINE_PART(8, 2, 1, 5, 1)
-#elif PF_DMA_PART == 9
-PF_DMA_DEFINE_PART(9, 2, 5, 1, 1)
-#else
-#define PF_DMA_DECLARE_PART(N) int pf_conv_dma_part##N##_launch(const pfconv::ConvGroups&, int, const pfconv::ConvGeom&, int, bool, hipStream_t);
-PF_DMA_DECLARE_PART(0) PF_DMA_DECLARE_PART(1) PF_DMA_DECLARE_PART(2) PF_DMA_DECLARE_PART(3)
-PF_DMA_DECLARE_PART(4) PF_DMA_DECLARE_PART(5) PF_DMA_DECLARE_PART(6) PF_DMA_DECLARE_PART(8) PF_DMA_DECLARE_PART(9)
-
-int pf_conv_dma_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, int nt, int roles,
-                       hipStream_t stream) {
-    for (int i = 0; i < ngroups; ++i)
-        if (!grp.d[i].zeros || grp.d[i].zeros_bytes < 128 * (grp.d[i].lds0 > grp.d[i].lds1 ? grp.d[i].lds0 : grp.d[i].lds1)) return PF_ERR_BAD_ARG;
-    const bool k33 = g.kh == 3 && g.kw == 3, k15 = g.kh == 1 && g.kw == 5, k51 = g.kh == 5 && g.kw == 1;
-    const bool f16 = grp.d[0].precision == PF_PREC_F16;
-    if (roles == 2) {           // 256 px x 64 channels per workgroup: half the weight bytes staged per output, twice the halo
-        if (k33) return pf_conv_dma_part0_launch(grp, ngroups, g, max_cout, f16, stream);
-        if (k15) return pf_conv_dma_part8_launch(grp, ngroups, g, max_cout, f16, stream);
-        if (k51) return pf_conv_dma_part9_launch(grp, ngroups, g, max_cout, f16, stream);
-        return PF_ERR_BAD_SHAPE;
-    }
-    if (nt == 2) {
-        if (k33) return pf_conv_dma_part1_launch(grp, ngroups, g, max_cout, f16, stream);
-        if (k15) return pf_conv_dma_part2_launch(grp, ngroups, g, max_cout, f16, stream);
-        if (k51) return pf_conv_dma_part3_launch(grp, ngroups, g, max_cout, f16, stream);
-    } else {
-        if (k33) return pf_conv_dma_part4_launch(grp, ngroups, g, max_cout, f16, stream);
-        if (k15) return pf_conv_dma_part5_launch(grp, ngroups, g, max_cout, f16, stream);
-        if (k51) return pf_conv_dma_part6_launch(grp, ngroups, g, max_cout, f16, stream);
-    }
-    return PF_ERR_BAD_SHAPE;
+template <int NT, int KH, int KW, int WN>
+int pf_conv_dma_shape_launch(const pfconv::ConvPlan& p, hipStream_t stream);
+#if PF_DMA_PART != 7
+template <int NT, int KH, int KW, int WN>
+int pf_conv_dma_shape_launch(const pfconv::ConvPlan& p, hipStream_t stream) {
+    return p.grp.d[0].precision == PF_PREC_F16 ? launch_conv_dma_t<NT, KH, KW, WN, true>(p.grp, p.ngroups, p.g, p.max_cout, stream)
+                                               : launch_conv_dma_t<NT, KH, KW, WN, false>(p.grp, p.ngroups, p.g, p.max_cout, stream);
 }
+#define PF_DMA_SHAPE(NT, KH, KW, WN) template int pf_conv_dma_shape_launch<NT, KH, KW, WN>(const pfconv::ConvPlan&, hipStream_t);
+#endif
+#if PF_DMA_PART == 0
+PF_DMA_SHAPE(2, 3, 3, 1)
+#elif PF_DMA_PART == 1
+PF_DMA_SHAPE(2, 3, 3, 2)
+#elif PF_DMA_PART == 2
+PF_DMA_SHAPE(2, 1, 5, 2)
+#elif PF_DMA_PART == 3
+PF_DMA_SHAPE(2, 5, 1, 2)
+#elif PF_DMA_PART == 4
+PF_DMA_SHAPE(1, 3, 3, 2)
+#elif PF_DMA_PART == 5
+PF_DMA_SHAPE(1, 1, 5, 2)
+#elif PF_DMA_PART == 6
+PF_DMA_SHAPE(1, 5, 1, 2)
+#elif PF_DMA_PART == 8
+PF_DMA_SHAPE(2, 1, 5, 1)
+#elif PF_DMA_PART == 9
+PF_DMA_SHAPE(2, 5, 1, 1)
+#else
+template <int NT, int WN>
+int pf_conv_dma_launch(const pfconv::ConvPlan& p, hipStream_t stream) {
+    const int kh = p.g.kh, kw = p.g.kw;
+    if (kh == 3 && kw == 3) return pf_conv_dma_shape_launch<NT, 3, 3, WN>(p, stream);
+    if (kh == 1 && kw == 5) return pf_conv_dma_shape_launch<NT, 1, 5, WN>(p, stream);
+    if (kh == 5 && kw == 1) return pf_conv_dma_shape_launch<NT, 5, 1, WN>(p, stream);
+    return PF_ERR_BAD_SHAPE;                // (no such instantiation: conv_plan names none)
+}
+template int pf_conv_dma_launch<2, 1>(const pfconv::ConvPlan&, hipStream_t);      // 256 px x 64 channels (roles 16 + 2)
+template int pf_conv_dma_launch<2, 2>(const pfconv::ConvPlan&, hipStream_t);      // 128 px x 128 channels (tile 4, roles 16 + 1)
+template int pf_conv_dma_launch<1, 2>(const pfconv::ConvPlan&, hipStream_t);      // 128 px x 64 channels (tiles 3, 8, roles 16 + 1)
 #endif

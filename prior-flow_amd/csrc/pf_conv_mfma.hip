@@ -848,56 +848,6 @@ int launch_conv_halo_t(const ConvGroups& grp, int ngroups, const ConvGeom& g, in
     return (int)hipGetLastError();
 }
 
-template <int NT, int KH, int KW, int WN>
-int launch_conv_ws_t(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout, hipStream_t stream);
-
-// Which form of the halo kernel a TH = 4 launch takes: 0 the symmetric pf_conv_halo_kernel, 1 pf_conv_ws_kernel with the
-// call's own 128-px tile (WN = 2), 2 pf_conv_ws_kernel with the 256 px x 64 channel tile (WN = 1; only where that still
-// gives every CU a workgroup).  PRIORFLOW_CONV_WS (A/B knob): 0 / 1 cap the choice, default 2.
-int conv_ws_choice(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout) {
-    static const int ws = [] { const char* e = getenv("PRIORFLOW_CONV_WS"); return e ? atoi(e) : 2; }();
-    if (ws <= 0) return 0;
-    const bool shape = (g.kh == 3 && g.kw == 3) || (g.kh == 1 && g.kw == 5) || (g.kh == 5 && g.kw == 1);
-    if (!shape || g.stride != 1) return 0;
-    for (int i = 0; i < ngroups; ++i)
-        if (grp.d[i].stats_out != nullptr || grp.d[i].in_scale != nullptr) return 0;
-    const long wgs256 = (long)(g.M / g.N) * ((g.H + 7) / 8) * ((g.W + 31) / 32) * ngroups * ((max_cout + 63) / 64);
-    // (measured: the 256-px tile wins for the 3x3 convs, -2 % at B=1; for 1x5 / 5x1 its taller halo costs more than the weights save)
-    if (ws >= 3 && g.kh == 3 && wgs256 >= 256) return 2;       // A/B: the 256 px x 64 channel roles kernel for Cout <= 64 as well
-    return (ws >= 2 && g.kh == 3 && max_cout > 64 && wgs256 >= 256) ? 2 : 1;
-}
-
-template <int NT, int TH>
-int launch_conv_halo(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout, hipStream_t stream) {
-    // every group of a launch must agree on having an input affine (one instantiation per launch)
-    bool affine = grp.d[0].in_scale != nullptr;
-    for (int i = 1; i < ngroups; ++i)
-        if ((grp.d[i].in_scale != nullptr) != affine) return PF_ERR_BAD_ARG;
-    if (affine) {                           // only the encoders' 3x3 convs use it
-        if (g.kh == 3 && g.kw == 3) return launch_conv_halo_t<NT, 3, 3, true, TH>(grp, ngroups, g, max_cout, stream);
-        return PF_ERR_BAD_SHAPE;
-    }
-    if constexpr (TH == 4) {                // role-specialised waves (pf_conv_ws_kernel); PRIORFLOW_CONV_WS=0: symmetric kernel
-        const int ws = conv_ws_choice(grp, ngroups, g, max_cout);
-        if (ws == 2) {
-            if (g.kh == 3 && g.kw == 3) return pf_conv_ws256_launch(grp, ngroups, g, max_cout, stream);   // (3x3 only: conv_ws_choice)
-        }
-        if (ws == 1) {
-            if (g.kh == 3 && g.kw == 3) return launch_conv_ws_t<NT, 3, 3, 2>(grp, ngroups, g, max_cout, stream);
-            if (g.kh == 1 && g.kw == 5) return launch_conv_ws_t<NT, 1, 5, 2>(grp, ngroups, g, max_cout, stream);
-            if (g.kh == 5 && g.kw == 1) return launch_conv_ws_t<NT, 5, 1, 2>(grp, ngroups, g, max_cout, stream);
-        }
-    }
-    if (g.kh == 3 && g.kw == 3) return launch_conv_halo_t<NT, 3, 3, false, TH>(grp, ngroups, g, max_cout, stream);
-    if (g.kh == 4 && g.kw == 4) return launch_conv_halo_t<NT, 4, 4, false, TH>(grp, ngroups, g, max_cout, stream);
-    if constexpr (TH == 4) {                // the GRU's separable convs and the 1x1 convs only exist at 1/8 resolution
-        if (g.kh == 1 && g.kw == 1) return launch_conv_halo_t<NT, 1, 1, false, TH>(grp, ngroups, g, max_cout, stream);
-        if (g.kh == 1 && g.kw == 5) return launch_conv_halo_t<NT, 1, 5, false, TH>(grp, ngroups, g, max_cout, stream);
-        if (g.kh == 5 && g.kw == 1) return launch_conv_halo_t<NT, 5, 1, false, TH>(grp, ngroups, g, max_cout, stream);
-    }
-    return PF_ERR_BAD_SHAPE;
-}
-
 template <int WM, int WN, int NT>
 int launch_conv(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout, bool split,
                 hipStream_t stream) {
@@ -1238,68 +1188,67 @@ int launch_conv_ws_t(const ConvGroups& grp, int ngroups, const ConvGeom& g, int 
 
 }  // namespace
 
+// The family launchers (pf_conv_priv.h): the plan names the instantiation, the shape of the launch completes it.
+template <int WM, int WN, int NT>
+int pf_conv_generic_launch(const ConvPlan& p, hipStream_t s) {
+    return launch_conv<WM, WN, NT>(p.grp, p.ngroups, p.g, p.max_cout, p.grp.d[0].precision == PF_PREC_BF16X3, s);
+}
+
+template <int NT, int TH>
+int pf_conv_halo_launch(const ConvPlan& p, hipStream_t s) {
+    const int kh = p.g.kh, kw = p.g.kw;
+    if (p.affine) return launch_conv_halo_t<NT, 3, 3, true, TH>(p.grp, p.ngroups, p.g, p.max_cout, s);   // (3x3 only: conv_plan)
+    if (kh == 3 && kw == 3) return launch_conv_halo_t<NT, 3, 3, false, TH>(p.grp, p.ngroups, p.g, p.max_cout, s);
+    if constexpr (NT < 3) {                 // (the 4x4 halo of the 256 px x 96 channel tile would not fit the LDS)
+        if (kh == 4 && kw == 4) return launch_conv_halo_t<NT, 4, 4, false, TH>(p.grp, p.ngroups, p.g, p.max_cout, s);
+    }
+    if constexpr (TH == 4) {                // the GRU's separable convs and the 1x1 convs only exist at 1/8 resolution
+        if (kh == 1 && kw == 1) return launch_conv_halo_t<NT, 1, 1, false, TH>(p.grp, p.ngroups, p.g, p.max_cout, s);
+        if (kh == 1 && kw == 5) return launch_conv_halo_t<NT, 1, 5, false, TH>(p.grp, p.ngroups, p.g, p.max_cout, s);
+        if (kh == 5 && kw == 1) return launch_conv_halo_t<NT, 5, 1, false, TH>(p.grp, p.ngroups, p.g, p.max_cout, s);
+    }
+    return PF_ERR_BAD_SHAPE;                // (no such instantiation: conv_plan names none)
+}
+
+template <int NT, int WN>
+int pf_conv_ws_launch(const ConvPlan& p, hipStream_t s) {
+    const int kh = p.g.kh, kw = p.g.kw;
+    if (kh == 3 && kw == 3) return launch_conv_ws_t<NT, 3, 3, WN>(p.grp, p.ngroups, p.g, p.max_cout, s);
+    if constexpr (WN == 2) {                // (the 256-px tile: 3x3 only, conv_ws_choice)
+        if (kh == 1 && kw == 5) return launch_conv_ws_t<NT, 1, 5, WN>(p.grp, p.ngroups, p.g, p.max_cout, s);
+        if (kh == 5 && kw == 1) return launch_conv_ws_t<NT, 5, 1, WN>(p.grp, p.ngroups, p.g, p.max_cout, s);
+    }
+    return PF_ERR_BAD_SHAPE;
+}
+
 // The product build compiles this file as five translation units in parallel (-DPF_CONV_PART=0..4, __graft_entry__.py):
-// each instantiates only the kernels its launcher names.  Without the macro (diagnostic builds: profiles/stamp_conv.py,
+// each instantiates only the kernels of its launchers.  Without the macro (diagnostic builds: profiles/stamp_conv.py,
 // profiles/ablate_conv.sh) everything is one unit.
 #ifndef PF_CONV_PART
 #define PF_CONV_PART (-1)
 #endif
 #define PF_PART(k) (PF_CONV_PART == -1 || PF_CONV_PART == (k))
 
-#if PF_PART(4)      // tile 8: halo kernel 256 px x 96 channels, 3x3 (round 6: the encoders' layer 2)
-int pf_conv_part4_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, hipStream_t s) {
-    if (g.kh != 3 || g.kw != 3) return PF_ERR_BAD_SHAPE;             // (the 4x4 halo of this tile would not fit the LDS)
-    const bool affine = grp.d[0].in_scale != nullptr;
-    for (int i = 1; i < ngroups; ++i)
-        if ((grp.d[i].in_scale != nullptr) != affine) return PF_ERR_BAD_ARG;
-    return affine ? launch_conv_halo_t<3, 3, 3, true, 8>(grp, ngroups, g, max_cout, s)
-                  : launch_conv_halo_t<3, 3, 3, false, 8>(grp, ngroups, g, max_cout, s);
-}
-#endif
-#if PF_PART(0)      // generic kernel (stride 2, exact fp32, small problems); the wave-organisation rule
-int pf_conv_ws_choice(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout) {
-    return conv_ws_choice(grp, ngroups, g, max_cout);
-}
-int pf_conv_part0_launch(int tile_id, const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout,
-                         bool split, hipStream_t s) {
-    switch (tile_id) {
-        case 0: return launch_conv<4, 1, 1>(grp, ngroups, g, max_cout, split, s);
-        case 1: return launch_conv<2, 2, 1>(grp, ngroups, g, max_cout, split, s);
-        case 7: return launch_conv<4, 1, 3>(grp, ngroups, g, max_cout, split, s);
-        default: return launch_conv<2, 2, 2>(grp, ngroups, g, max_cout, split, s);
-    }
-}
+#if PF_PART(0)      // generic kernel (stride 2, exact fp32, small problems): tiles 0, 1, 2, 7
+template int pf_conv_generic_launch<4, 1, 1>(const ConvPlan&, hipStream_t);
+template int pf_conv_generic_launch<2, 2, 1>(const ConvPlan&, hipStream_t);
+template int pf_conv_generic_launch<2, 2, 2>(const ConvPlan&, hipStream_t);
+template int pf_conv_generic_launch<4, 1, 3>(const ConvPlan&, hipStream_t);
 #endif
 #if PF_PART(1)      // tile 3: halo / role-specialised kernels, 128 px x 64 channels
-int pf_conv_part1_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, hipStream_t s) {
-    return launch_conv_halo<1, 4>(grp, ngroups, g, max_cout, s);
-}
+template int pf_conv_halo_launch<1, 4>(const ConvPlan&, hipStream_t);
+template int pf_conv_ws_launch<1, 2>(const ConvPlan&, hipStream_t);
 #endif
 #if PF_PART(2)      // tile 4: 128 px x 128 channels
-int pf_conv_part2_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, hipStream_t s) {
-    return launch_conv_halo<2, 4>(grp, ngroups, g, max_cout, s);
-}
+template int pf_conv_halo_launch<2, 4>(const ConvPlan&, hipStream_t);
+template int pf_conv_ws_launch<2, 2>(const ConvPlan&, hipStream_t);
 #endif
 #if PF_PART(3)      // tile 5: 8-row halo kernel; the role-specialised 256 px x 64 channel tile of the 3x3 convs
-int pf_conv_part3_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, hipStream_t s) {
-    return launch_conv_halo<2, 8>(grp, ngroups, g, max_cout, s);
-}
-int pf_conv_ws256_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, hipStream_t s) {
-    return launch_conv_ws_t<2, 3, 3, 1>(grp, ngroups, g, max_cout, s);
-}
+template int pf_conv_halo_launch<2, 8>(const ConvPlan&, hipStream_t);
+template int pf_conv_ws_launch<2, 1>(const ConvPlan&, hipStream_t);
 #endif
-
-#if PF_CONV_PART == -1
-int pf_conv_kernels_launch(int tile_id, const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout,
-                           bool split, hipStream_t s) {
-    switch (tile_id) {
-        case 0: case 1: case 2: case 7: return pf_conv_part0_launch(tile_id, grp, ngroups, g, max_cout, split, s);
-        case 3: return pf_conv_part1_launch(grp, ngroups, g, max_cout, s);
-        case 4: return pf_conv_part2_launch(grp, ngroups, g, max_cout, s);
-        case 8: return pf_conv_part4_launch(grp, ngroups, g, max_cout, s);
-        default: return pf_conv_part3_launch(grp, ngroups, g, max_cout, s);
-    }
-}
+#if PF_PART(4)      // tile 8: halo kernel 256 px x 96 channels, 3x3 (round 6: the encoders' layer 2)
+template int pf_conv_halo_launch<3, 8>(const ConvPlan&, hipStream_t);
 #endif
 
 #if defined(PF_STAMPS) && PF_CONV_PART == -1

@@ -373,26 +373,30 @@ __device__ __forceinline__ void tile_epilogue(const pf_conv_desc& d, const f32x1
     else tile_epilogue_t<NT, CHECK, true>(d, acc, jb, li, p0, plimit);
 }
 
+// The plan of one pf_conv2d launch (pf_conv_api.hip: conv_plan): the validated groups and geometry, the codes the host queries
+// report (pf_conv2d_tile / _roles / _stats_blocks) and the launcher of the kernel instantiation pf_conv2d runs.
+struct ConvPlan {
+    ConvGroups grp; ConvGeom g; int ngroups, max_cout;
+    int tile, roles, stats_blocks;
+    bool affine;                                        // halo kernel: every group has an input affine (pf_conv_desc.in_scale)
+    int (*launch)(const ConvPlan& p, hipStream_t stream);
+};
+
 }  // namespace pfconv
 
-// pf_conv_mfma.hip (compiled as four units, PF_CONV_PART): kernels by pf_conv2d_tile code -- part 0: tiles 0..2 (generic
-// kernel), part 1: tile 3, part 2: tile 4, part 3: tile 5 and the 256-px role-specialised tile; pf_conv_ws_choice: which
-// wave organisation a TH = 4 launch takes (pf_conv2d_roles).
-int pf_conv_part0_launch(int tile_id, const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout,
-                         bool split, hipStream_t stream);
-int pf_conv_part1_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, hipStream_t stream);
-int pf_conv_part2_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, hipStream_t stream);
-int pf_conv_part3_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, hipStream_t stream);
-int pf_conv_part4_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, hipStream_t stream);
-int pf_conv_ws256_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, hipStream_t stream);
-int pf_conv_ws_choice(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout);
+// Kernel launchers, one per instantiation family: the template arguments are the plan's choice, the rest of the instantiation
+// follows the launch (KH, KW: g.kh, g.kw; SPLIT / F16: the precision; AFFINE: p.affine).  None of them decides or refuses anything.
+// pf_conv_mfma.hip, compiled as five units (PF_CONV_PART): 0 the generic kernel, 1..4 the halo / role-split kernels with
+// (NT, TH) = (1, 4), (2, 4), (2, 8), (3, 8) -- tiles 3, 4, 5, 8 (a role-split kernel's TH is 8 / WN).
+template <int WM, int WN, int NT> int pf_conv_generic_launch(const pfconv::ConvPlan& p, hipStream_t stream);
+template <int NT, int TH> int pf_conv_halo_launch(const pfconv::ConvPlan& p, hipStream_t stream);
+template <int NT, int WN> int pf_conv_ws_launch(const pfconv::ConvPlan& p, hipStream_t stream);
 
 // pf_enc_conv.hip: the weights-stationary kernel of the encoders' 3x3 64 -> 64 convolutions (round 5)
 bool pf_enc_conv64_applies(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout);
 int pf_enc_conv64_stats_blocks(const pfconv::ConvGeom& g);
-int pf_enc_conv64_launch(const pfconv::ConvGroups& grp, const pfconv::ConvGeom& g, hipStream_t stream);
+int pf_enc_conv64_launch(const pfconv::ConvPlan& p, hipStream_t stream);
 
-// pf_conv_dma.hip: launcher of the all-DMA kernel.  `roles` as in pf_conv2d_roles (1: 128-px tile, 2: 256 px x 64 channels);
-// the operand form (split twins or f16 maps) follows grp.d[0].precision.
-int pf_conv_dma_launch(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout, int nt, int roles,
-                       hipStream_t stream);
+// pf_conv_dma.hip: the all-DMA kernel pf_conv_dma_kernel<NT, KH, KW, WN, F16>; the operand form (split twins or f16 maps)
+// follows grp.d[0].precision.
+template <int NT, int WN> int pf_conv_dma_launch(const pfconv::ConvPlan& p, hipStream_t stream);

@@ -337,7 +337,7 @@ pf_enc_conv64_kernel(const EcArgs a) {
 
 }  // namespace
 
-// Whether pf_conv2d hands this launch to pf_enc_conv64_kernel (PRIORFLOW_ENC_CONV64=0: never): one group, 3x3 stride 1, 64 -> 64,
+// Whether pf_conv2d's plan hands this launch to pf_enc_conv64_kernel (PRIORFLOW_ENC_CONV64=0: never): one group, 3x3 stride 1, 64 -> 64,
 // fp32 rows in and out, LINEAR, RELU or RELU_RES epilogue, a map of whole 32-column strips and 4-row steps that fills the chip.
 bool pf_enc_conv64_applies(const pfconv::ConvGroups& grp, int ngroups, const pfconv::ConvGeom& g, int max_cout) {
     static const int mode = [] { const char* e = getenv("PRIORFLOW_ENC_CONV64"); return e ? atoi(e) : 1; }();     // 2: also on small maps (tests)
@@ -364,8 +364,9 @@ static int ec_segment(const pfconv::ConvGeom& g) {
 // fp64 statistics partials per image of a launch with stats_out: one per (segment, row phase of the 4-row step, strip)
 int pf_enc_conv64_stats_blocks(const pfconv::ConvGeom& g) { return (g.H / ec_segment(g)) * 4 * (g.W / 32); }
 
-int pf_enc_conv64_launch(const pfconv::ConvGroups& grp, const pfconv::ConvGeom& g, hipStream_t stream) {
-    const pf_conv_desc& d = grp.d[0];
+int pf_enc_conv64_launch(const pfconv::ConvPlan& p, hipStream_t stream) {
+    const pf_conv_desc& d = p.grp.d[0];
+    const pfconv::ConvGeom& g = p.g;
     EcArgs a;
     a.in = d.in0 + d.off0; a.ld_in = d.ld0;
     a.w = reinterpret_cast<const char*>(d.weight); a.bias = d.bias;

@@ -150,6 +150,108 @@ def test_co_groups_hint_keeps_the_two_group_tile(built_lib):
     assert lib._dll.pf_conv2d_tile(bad, 1, 1, 64, 128) < 0            # more co-launched groups than a launch can hold: refused
 
 
+def _plan_desc(cin=64, cout=64, kh=3, kw=3, prec=1, form="fp32", **fields):
+    """One descriptor for the planning queries (pointers are never dereferenced): fp32 rows, or pre-split operands
+    (split twins, f16 maps for prec 2) with their zero block."""
+    from prior_flow_amd import _lib
+    fake = 0x1000
+    d = _lib.ConvDesc()
+    cpc = 64 if prec == _lib.PREC_F16 else 32
+    if form == "fp32":
+        d.in0, d.ld0 = fake, cin
+    else:
+        d.in0_split, d.lds0 = fake, (cin + cpc - 1) // cpc
+        d.zeros, d.zeros_bytes = fake, 4096
+    d.c0, d.weight, d.bias = cin, fake, fake
+    d.out, d.ld_out, d.cout = fake, cout, cout
+    d.kh, d.kw, d.stride, d.epilogue, d.scale, d.precision = kh, kw, 1, _lib.EPI_RELU, 1.0, prec
+    for name, v in fields.items():
+        setattr(d, name, v)
+    return d
+
+
+def _plan(lib, ds, B, H, W):
+    """(pf_conv2d_tile, pf_conv2d_roles, pf_conv2d_stats_blocks) of one launch."""
+    from prior_flow_amd import _lib
+    a = (_lib.ConvDesc * len(ds))(*ds)
+    return tuple(int(f(a, len(ds), B, H, W)) for f in (lib._dll.pf_conv2d_tile, lib._dll.pf_conv2d_roles, lib._dll.pf_conv2d_stats_blocks))
+
+
+def _enc_conv64_stats_blocks(B, H, W):
+    """The weights-stationary kernel's partials per image: one per (segment of rows, row phase, strip), with the longest
+    segment (a divisor of H, a multiple of 8) that still gives every CU a work item (csrc/pf_enc_conv.hip)."""
+    seg = next((s for s in range(H, 8, -8) if H % s == 0 and B * (H // s) * (W // 32) >= 256), 8)
+    return H // seg * 4 * (W // 32)
+
+
+def test_plan_invariants_over_product_launches(built_lib):
+    """The three queries read one plan, the one pf_conv2d executes: a nonzero roles code (>= 16: the all-DMA kernel) only on the
+    halo tiles 3, 4, 5 and 8; the generic tiles 0, 1, 2, 7 and the weights-stationary kernel (tile 6) report roles 0, and
+    tile 6 reports that kernel's statistics blocks."""
+    from prior_flow_amd import _lib
+    lib = _lib.PfLib(_lib.LIB_PATH, require_cuda=False)
+    seen = set()
+    for prec, form in ((_lib.PREC_F32, "fp32"), (_lib.PREC_BF16X3, "fp32"), (_lib.PREC_BF16X3, "split"), (_lib.PREC_F16, "split")):
+        for cin, cout, kh, kw, stride in ((64, 64, 3, 3, 1), (96, 96, 3, 3, 1), (128, 256, 3, 3, 1), (256, 128, 1, 5, 1),
+                                          (256, 384, 5, 1, 1), (256, 2, 1, 1, 1), (128, 64, 4, 4, 1), (64, 96, 3, 3, 2), (96, 128, 1, 1, 2)):
+            for B, H, W in ((1, 64, 128), (2, 32, 64), (4, 256, 512), (8, 64, 128), (32, 64, 128), (1, 80, 160), (1, 37, 53)):
+                for ng in (1, 2):
+                    ds = [_plan_desc(cin, cout, kh, kw, prec, form, stride=stride) for _ in range(ng)]
+                    tile, roles, nblk = _plan(lib, ds, B, H, W)
+                    if tile < 0:
+                        assert tile == roles == nblk, (prec, form, cin, cout, kh, kw, B, H, W, ng)
+                        continue
+                    seen.add((tile, roles))
+                    if roles != 0:
+                        assert tile in (3, 4, 5, 8), (tile, roles)
+                    if tile in (0, 1, 2, 6, 7):
+                        assert roles == 0, (tile, roles)
+                    if tile == 6:
+                        assert nblk == _enc_conv64_stats_blocks(B, H, W)
+                    if form == "split" and stride == 1 and (kh, kw) in ((3, 3), (1, 5), (5, 1)):
+                        assert roles in (17, 18), (tile, roles)
+    # the sweep reaches every kind of plan: generic, halo, role-split, weights-stationary and all-DMA
+    assert {t for t, _ in seen} >= {0, 1, 3, 4, 5, 6, 7, 8}, seen
+    assert {r for _, r in seen} >= {0, 1, 2, 17, 18}, seen
+    # a launch that takes the weights-stationary kernel has no wave organisation of the halo kernel (fnet's layer 1 at 512x1024)
+    assert _plan(lib, [_plan_desc()], 4, 256, 512) == (6, 0, _enc_conv64_stats_blocks(4, 256, 512))
+
+
+def test_launch_time_refusals_are_reported_by_every_query(built_lib):
+    """A descriptor pf_conv2d refuses gets that refusal's PF_ERR_* code from all three queries, not a tile."""
+    from prior_flow_amd import _lib
+    lib = _lib.PfLib(_lib.LIB_PATH, require_cuda=False)
+    fake, BAD_ARG, BAD_SHAPE = 0x1000, -1, -2
+    d = _plan_desc
+    affine = dict(in_scale=fake, in_shift=fake)
+    cases = [
+        # the input affine on a generic tile (stride 2)
+        ("affine, generic tile", [d(64, 96, stride=2, **affine)], (4, 64, 128), BAD_SHAPE),
+        # fused statistics with another epilogue than LINEAR, on fp32 arithmetic or pixel tiles straddling images (generic kernel)
+        ("stats, RELU", [d(128, 128, stats_out=fake)], (1, 64, 128), BAD_SHAPE),
+        ("stats, generic fp32", [d(64, 96, prec=_lib.PREC_F32, stride=2, stats_out=fake, epilogue=_lib.EPI_LINEAR)], (1, 32, 64), BAD_SHAPE),
+        ("stats, generic straddling", [d(64, 96, stride=2, stats_out=fake, epilogue=_lib.EPI_LINEAR)], (1, 10, 20), BAD_SHAPE),
+        # accumulator start values off the all-DMA kernel
+        ("pre, fp32 operands", [d(128, 128, pre=fake, ld_pre=128)], (1, 64, 128), BAD_SHAPE),
+        # no fp32 operand where the all-DMA kernel does not go (1x1; fused statistics)
+        ("split only, 1x1", [d(256, 128, 1, 1, form="split")], (1, 64, 128), BAD_ARG),
+        ("split only, stats", [d(128, 128, form="split", stats_out=fake, epilogue=_lib.EPI_LINEAR)], (1, 64, 128), BAD_ARG),
+        # the all-DMA kernel without its zero block
+        ("no zero block", [d(128, 128, form="split", zeros=None, zeros_bytes=0)], (1, 64, 128), BAD_ARG),
+        ("short zero block", [d(256, 128, form="split", zeros_bytes=512)], (1, 64, 128), BAD_ARG),
+        # halo tiles: groups that disagree on the input affine; the input affine on another shape than 3x3
+        ("affine mismatch", [d(128, 128, **affine), d(128, 128)], (1, 64, 128), BAD_ARG),
+        ("affine, 1x5", [d(128, 128, 1, 5, **affine)], (1, 64, 128), BAD_SHAPE),
+    ]
+    for name, ds, geo, code in cases:
+        assert _plan(lib, ds, *geo) == (code, code, code), name
+    # the same launches without the fault are planned
+    assert _plan(lib, [d(64, 96, stride=2)], 4, 64, 128)[0] in (0, 1, 2, 7)
+    assert _plan(lib, [d(128, 128, **affine)], 1, 64, 128)[0] in (3, 4)
+    assert _plan(lib, [d(128, 128, epilogue=_lib.EPI_LINEAR, stats_out=fake)], 1, 64, 128)[0] in (3, 4)
+    assert _plan(lib, [d(128, 128, form="split")], 1, 64, 128)[1] in (17, 18)
+
+
 def test_every_profiled_kernel_has_its_counter_evidence():
     """a new default kernel shipped without its PMC entry and the driver's bench line carried `traffic: null` for the
     headline kernel.  Every library kernel the committed bench line of the current round names (`kernels_by_time`, the roofline
