@@ -55,6 +55,20 @@ int pf_normalise_images(const float* image1, const float* image2, float* f1, flo
 int pf_prepare_images(const float* image1, const float* image2, const float* grid, float* img_f, float* img_c,
                       int B, int H, int W, void* stream);
 
+/* The input stage of ONE frame (video streams): out = [im | im_B] ([2B,3,H,W]), bit-identical to img_c of pf_prepare_images with
+ * image1 = image.  image: [B,3,H,W], values 0..255; grid as in pf_prepare_images. */
+int pf_prepare_frame(const float* image, const float* grid, float* out, int B, int H, int W, void* stream);
+
+/* forward_interpolate (core/utils/utils.py:30-58): the warm start of a flow sequence, batched.  flow, out: planar [B,2,h,w].
+ * Source pixel (x0, y0) moves to (x1, y1) = (x0 + u, y0 + v) (float64); it is a valid point iff 0 < x1 < w and 0 < y1 < h
+ * (strict).  Every pixel of out takes the (u, v) of the valid point nearest to it (Euclidean, float64; equally near: the lowest
+ * source raster index); an image without a valid point gives zeros.  wrap = 1 (ERP): x1 is taken modulo w, the x test always
+ * holds, and x distances wrap, min(|dx|, w - |dx|).  Exact: a counting sort of the points into unit cells and a ring search
+ * per pixel (five launches, no host synchronisation).  scratch: device memory of at least 4 * B * (3 * h * w + 1) bytes,
+ * overwritten.  PF_ERR_BAD_ARG: a NULL pointer, flow == out, wrap not 0 / 1 or scratch_bytes too small. */
+int pf_forward_interpolate(const float* flow, float* out, void* scratch, long scratch_bytes, int B, int h, int w, int wrap,
+                           void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

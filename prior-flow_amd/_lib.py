@@ -85,6 +85,8 @@ _SIGNATURES = {
     "pf_img_rotate": [_fp, _fp, _fp, _i, _i, _i, _i, _fp],
     "pf_normalise_images": [_fp, _fp, _fp, _fp, _fp, C.c_long, _fp],
     "pf_prepare_images": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp],
+    "pf_prepare_frame": [_fp, _fp, _fp, _i, _i, _i, _fp],
+    "pf_forward_interpolate": [_fp, _fp, _fp, C.c_long, _i, _i, _i, _i, _fp],
     "pf_flow_prep": [_fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _i, _fp],
     "pf_flo_rotate": [_fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _i, _fp],
     "pf_corr_pyramid": [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp],
@@ -301,6 +303,33 @@ class PfLib:
             raise PfError("prepare_images: operand shapes do not fit")
         self._rc(self._dll.pf_prepare_images(_ptr(image1), _ptr(image2), _ptr(grid), _ptr(img_f), _ptr(img_c), B, H, W,
                                              self._stream(image1)), "pf_prepare_images")
+
+    def prepare_frame(self, image, grid, out):
+        """The input stage of one frame: out = [im | im_B] ([2B,3,H,W]), bit-identical to prepare_images' img_c for image1 = image."""
+        self._chk(image, grid, out)
+        B, Cc, H, W = image.shape
+        if not (Cc == 3 and tuple(grid.shape) == (2, H, W) and tuple(out.shape) == (2 * B, 3, H, W)):
+            raise PfError("prepare_frame: operand shapes do not fit")
+        self._rc(self._dll.pf_prepare_frame(_ptr(image), _ptr(grid), _ptr(out), B, H, W, self._stream(image)), "pf_prepare_frame")
+        return out
+
+    @staticmethod
+    def forward_interpolate_scratch_bytes(B: int, h: int, w: int) -> int:
+        """Scratch of pf_forward_interpolate: cell counts / offsets, ranks and the sorted points (int32)."""
+        return 4 * B * (3 * h * w + 1)
+
+    def forward_interpolate(self, flow, out, scratch, wrap: bool = False):
+        """forward_interpolate (core/utils/utils.py:30-58) of planar flows [B,2,h,w] into out; scratch: a device tensor of at least
+        forward_interpolate_scratch_bytes(B, h, w) bytes (any dtype; overwritten)."""
+        self._chk(flow, out)
+        if flow.dim() != 4 or flow.shape[1] != 2 or tuple(out.shape) != tuple(flow.shape):
+            raise PfError(f"forward_interpolate: flow {tuple(flow.shape)} / out {tuple(out.shape)}: expected two [B,2,h,w] tensors")
+        if not scratch.is_contiguous() or (self.require_cuda and not scratch.is_cuda):
+            raise PfError("forward_interpolate: scratch must be a contiguous device tensor")
+        B, _, h, w = flow.shape
+        self._rc(self._dll.pf_forward_interpolate(_ptr(flow), _ptr(out), _ptr(scratch), scratch.numel() * scratch.element_size(),
+                                                  B, h, w, int(bool(wrap)), self._stream(flow)), "pf_forward_interpolate")
+        return out
 
     def flow_prep(self, coords1, flow_out=None, d0=None, d0_off=0, d1=None, d1_off=0):
         self._chk(coords1, flow_out, d0, d1)

@@ -42,6 +42,39 @@ extern "C" int pf_prepare_images(const float* image1, const float* image2, const
     return PF_LAUNCH(prepare_images, a, (long)B * 3 * H * W, stream);
 }
 
+extern "C" int pf_prepare_frame(const float* image, const float* grid, float* out, int B, int H, int W, void* stream) {
+    PF_REQUIRE(image && grid && out && out != image);
+    PF_REQUIRE_SHAPE(B > 0 && H > 1 && W > 1);
+    PfPrepFrameArgs a; a.image = image; a.grid = grid; a.out = out; a.B = B; a.H = H; a.W = W;
+    return PF_LAUNCH(prepare_frame, a, (long)B * 3 * H * W, stream);
+}
+
+#if !defined(PF_FI_SCAN_LAUNCH) && !defined(__HIPCC__)
+// host build (tests/emu): the scan as its host statement, one image after the other (the device build defines the macro as the
+// one-workgroup-per-image scan kernel of pf_elem_kernels.hip and never falls back to this)
+static int pf_fi_scan_host(const PfFwdInterpArgs& a, void*) {
+    for (int b = 0; b < a.B; ++b) pf_fi_scan_image(a, b);
+    return PF_OK;
+}
+#define PF_FI_SCAN_LAUNCH(a, stream) pf_fi_scan_host(a, stream)
+#endif
+
+extern "C" int pf_forward_interpolate(const float* flow, float* out, void* scratch, long scratch_bytes, int B, int h, int w,
+                                      int wrap, void* stream) {
+    PF_REQUIRE(flow && out && scratch && flow != out && (wrap == 0 || wrap == 1));
+    PF_REQUIRE_SHAPE(B > 0 && h > 0 && w > 0 && (long)h * w < (1L << 30));
+    const long hw = (long)h * w;
+    PF_REQUIRE(scratch_bytes >= 4L * B * (3 * hw + 1));
+    PfFwdInterpArgs a; a.flow = flow; a.out = out; a.B = B; a.h = h; a.w = w; a.wrap = wrap;
+    a.cell = (int*)scratch; a.rank = a.cell + B * (hw + 1); a.sorted = a.rank + B * hw;
+    int rc = PF_LAUNCH(fi_zero, a, B * (hw + 1), stream);
+    if (rc == PF_OK) rc = PF_LAUNCH(fi_count, a, B * hw, stream);
+    if (rc == PF_OK) rc = PF_FI_SCAN_LAUNCH(a, stream);
+    if (rc == PF_OK) rc = PF_LAUNCH(fi_scatter, a, B * hw, stream);
+    if (rc == PF_OK) rc = PF_LAUNCH(fi_search, a, B * hw, stream);
+    return rc;
+}
+
 extern "C" int pf_flow_prep(const float* coords1, float* flow_out, float* d0, int d0_ld, int d0_off,
                             float* d1, int d1_ld, int d1_off, int B, int H8, int W8, void* stream) {
     PF_REQUIRE(coords1);

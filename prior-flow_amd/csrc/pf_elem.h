@@ -334,6 +334,33 @@ PF_HD void pf_prepare_images_elem(long idx, const PfPrepImgArgs& a) {   // idx o
     if (a.c) { a.c[o] = v1; a.c[img + o] = r1; }
 }
 
+// The input stage of ONE frame (video streams, prior-flow_amd/video.py): out = [im | im_B] ([2B,3,H,W]) -- the image1 half of
+// pf_prepare_images, the same pixel order, taps, products and sums: bit-identical to img_c of a pf_prepare_images launch.
+struct PfPrepFrameArgs { const float* image; const float* grid; float* out; int B, H, W; };
+PF_HD void pf_prepare_frame_elem(long idx, const PfPrepFrameArgs& a) {   // idx over B*3*H*W
+    const long hw = (long)a.H * a.W;
+    const long plane = (idx / hw) * hw;
+    long pix = idx % hw;
+    if (!((a.H | a.W) & 7)) {                       // 8 x 8 pixel tiles (pf_prepare_images_elem)
+        const long tile = pix >> 6;
+        const int in = (int)(pix & 63), tpr = a.W >> 3;
+        pix = ((tile / tpr) * 8 + (in >> 3)) * a.W + (tile % tpr) * 8 + (in & 7);
+    }
+    const float gx = pf_pymod(a.grid[pix], (float)a.W);
+    const float gy = a.grid[hw + pix];
+    const PfTaps t = pf_taps0(gx, gy, a.H, a.W);
+    const long img = (long)a.B * 3 * hw;
+    const float* p1 = a.image + plane;
+    const float o1 = p1[pix];
+    float t1[4];
+    for (int q = 0; q < 4; ++q) t1[q] = p1[t.idx[q]];
+    float r1 = pf_norm255(t1[0]) * t.w[0];
+    for (int q = 1; q < 4; ++q) r1 = r1 + pf_norm255(t1[q]) * t.w[q];
+    const long o = plane + pix;
+    a.out[o] = pf_norm255(o1);
+    a.out[img + o] = r1;
+}
+
 // ----------------------------------------------------------------------------------------------
 // flow = coords1 - coords0, scattered to planar + up to two channel-last destinations
 // (core/prior_raft.py:172,177; coords_grid core/utils/utils.py:98-101)
@@ -1496,3 +1523,129 @@ PF_HD void pf_warp_gcorr_bwd_elem(long idx, const PfWarpGcorrBwdArgs& a) {   // 
         if (t.w[j] != 0.f) PF_ATOMIC_ADD(d2 + (long)t.idx[j] * a.C, v * t.w[j]);
 }
 
+
+// ----------------------------------------------------------------------------------------------
+// forward_interpolate (core/utils/utils.py:30-58, RAFT's warm start of a sequence): every pixel (x0, y0) of a flow field moves to
+// (x1, y1) = (x0 + u, y0 + v); a moved point is valid iff 0 < x1 < w and 0 < y1 < h (wrap: x1 taken modulo w, only the y test);
+// every grid pixel takes the (u, v) of the valid point nearest to it (griddata 'nearest'; wrap: x distances wrap).  Positions and
+// distances are float64 as in the reference (int grid + float32 flow in numpy); equally near points: the lowest source index.
+// Exact search in four passes over a counting sort of the valid points into the unit cells of the grid:
+//   pf_fi_zero    cell counts = 0                                cell: [B][h*w + 1] (counts, then exclusive offsets + total)
+//   pf_fi_count   rank of a valid point in its cell (atomic)     rank: [B][h*w] (-1: invalid)
+//   (scan)        counts -> exclusive offsets per image          (PF_FI_SCAN_LAUNCH: one workgroup per image)
+//   pf_fi_scatter sorted[offset(cell) + rank] = source pixel     sorted: [B][h*w]
+//   pf_fi_search  rings of cells around each target pixel, until no cell left can hold a nearer point
+// ----------------------------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PF_ATOMIC_INC_I32(ptr) atomicAdd((ptr), 1)
+#else
+#define PF_ATOMIC_INC_I32(ptr) __atomic_fetch_add((ptr), 1, __ATOMIC_RELAXED)
+#endif
+struct PfFwdInterpArgs { const float* flow; float* out; int* cell; int* rank; int* sorted; int B, h, w, wrap; };
+
+// moved position of source pixel s of image b (float64; numpy's int + float32 -> float64), false when it is not a valid point
+PF_HD bool pf_fi_moved(const PfFwdInterpArgs& a, int b, int s, double& x1, double& y1) {
+    const long hw = (long)a.h * a.w;
+    const float* f = a.flow + (long)b * 2 * hw;
+    x1 = (double)(s % a.w) + (double)f[s];
+    y1 = (double)(s / a.w) + (double)f[hw + s];
+    if (!(y1 > 0.0 && y1 < (double)a.h)) return false;                 // (NaN: invalid)
+    if (!a.wrap) return x1 > 0.0 && x1 < (double)a.w;
+    if (!(x1 - x1 == 0.0)) return false;                                // +-inf / NaN have no position modulo w
+    double m = fmod(x1, (double)a.w);                                  // numpy's float remainder: the sign of w
+    if (m < 0.0) m += (double)a.w;                                     // (may round to w itself, which is 0 modulo w)
+    x1 = m;
+    return true;
+}
+PF_HD int pf_fi_cell(const PfFwdInterpArgs& a, double x1, double y1) {
+    int cx = (int)floor(x1);
+    if (cx >= a.w) cx -= a.w;                                           // wrap: x1 == w lies in cell 0
+    return (int)floor(y1) * a.w + cx;
+}
+
+PF_HD void pf_fi_zero_elem(long idx, const PfFwdInterpArgs& a) { a.cell[idx] = 0; }   // idx over B*(h*w + 1)
+
+PF_HD void pf_fi_count_elem(long idx, const PfFwdInterpArgs& a) {      // idx over B*h*w: one source pixel
+    const long hw = (long)a.h * a.w;
+    const int b = (int)(idx / hw), s = (int)(idx % hw);
+    double x1, y1;
+    a.rank[idx] = pf_fi_moved(a, b, s, x1, y1) ? PF_ATOMIC_INC_I32(a.cell + b * (hw + 1) + pf_fi_cell(a, x1, y1)) : -1;
+}
+
+PF_HD void pf_fi_scatter_elem(long idx, const PfFwdInterpArgs& a) {    // idx over B*h*w: one source pixel
+    const int r = a.rank[idx];
+    if (r < 0) return;
+    const long hw = (long)a.h * a.w;
+    const int b = (int)(idx / hw), s = (int)(idx % hw);
+    double x1, y1;
+    pf_fi_moved(a, b, s, x1, y1);
+    a.sorted[b * hw + a.cell[b * (hw + 1) + pf_fi_cell(a, x1, y1)] + r] = s;
+}
+
+// the points of cell (cy, cx) against the best so far (squared float64 distance, then the lower source index)
+PF_HD void pf_fi_visit(const PfFwdInterpArgs& a, int b, int cy, int cx, int x, int y, double& best, int& best_s) {
+    const long hw = (long)a.h * a.w;
+    const int* off = a.cell + b * (hw + 1);
+    const int* srt = a.sorted + b * hw;
+    const int c = cy * a.w + cx;
+    for (int k = off[c]; k < off[c + 1]; ++k) {
+        const int s = srt[k];
+        double x1, y1;
+        pf_fi_moved(a, b, s, x1, y1);
+        double dx = fabs(x1 - (double)x);
+        if (a.wrap) dx = fmin(dx, (double)a.w - dx);
+        const double dy = y1 - (double)y;
+        const double d2 = dx * dx + dy * dy;
+        if (d2 < best || (d2 == best && s < best_s)) { best = d2; best_s = s; }
+    }
+}
+
+// One target pixel.  Ring r holds the cells at Chebyshev distance r in cell units (x: cyclic when wrapping) from the target's own
+// cell; every point of a cell outside rings 0..r lies MORE than r pixels away, so the search stops after ring r once the best
+// squared distance is <= r^2 (a point of a later ring can be neither nearer nor as near).
+PF_HD void pf_fi_search_elem(long idx, const PfFwdInterpArgs& a) {     // idx over B*h*w
+    const long hw = (long)a.h * a.w;
+    const int b = (int)(idx / hw), p = (int)(idx % hw);
+    const int y = p / a.w, x = p % a.w, w = a.w;
+    float* o = a.out + (long)b * 2 * hw;
+    const float* f = a.flow + (long)b * 2 * hw;
+    double best = 0.0;
+    int best_s = -1;
+    if (a.cell[b * (hw + 1) + hw] > 0) {                                // no valid point: zeros (scipy would raise)
+        best = 1e300;
+        const int rx = a.wrap ? w / 2 : (x > w - 1 - x ? x : w - 1 - x);
+        const int ry = y > a.h - 1 - y ? y : a.h - 1 - y;
+        const int rmax = rx > ry ? rx : ry;
+        for (int r = 0; r <= rmax; ++r) {
+            const int y0 = y - r < 0 ? 0 : y - r, y1 = y + r > a.h - 1 ? a.h - 1 : y + r;
+            for (int cy = y0; cy <= y1; ++cy) {
+                if (cy == y - r || cy == y + r) {                       // a top / bottom row of the ring: columns within r
+                    int lo = x - r, hi = x + r;
+                    if (a.wrap && 2 * r + 1 >= w) { lo = 0; hi = w - 1; }
+                    if (!a.wrap) { lo = lo < 0 ? 0 : lo; hi = hi > w - 1 ? w - 1 : hi; }
+                    for (int c = lo; c <= hi; ++c) pf_fi_visit(a, b, cy, a.wrap ? (c % w + w) % w : c, x, y, best, best_s);
+                } else if (r > 0) {                                     // a side of the ring: the columns exactly r away
+                    if (a.wrap) {
+                        if (2 * r <= w) pf_fi_visit(a, b, cy, ((x - r) % w + w) % w, x, y, best, best_s);
+                        if (2 * r < w) pf_fi_visit(a, b, cy, (x + r) % w, x, y, best, best_s);
+                    } else {
+                        if (x - r >= 0) pf_fi_visit(a, b, cy, x - r, x, y, best, best_s);
+                        if (x + r < w) pf_fi_visit(a, b, cy, x + r, x, y, best, best_s);
+                    }
+                }
+            }
+            if (best_s >= 0 && best <= (double)r * (double)r) break;
+        }
+    }
+    o[p] = best_s >= 0 ? f[best_s] : 0.f;
+    o[hw + p] = best_s >= 0 ? f[hw + best_s] : 0.f;
+}
+
+// counts -> exclusive offsets of one image (and the total at [h*w]); the host statement of the device scan
+PF_HD void pf_fi_scan_image(const PfFwdInterpArgs& a, int b) {
+    const long hw = (long)a.h * a.w;
+    int* c = a.cell + b * (hw + 1);
+    int s = 0;
+    for (long i = 0; i < hw; ++i) { const int v = c[i]; c[i] = s; s += v; }
+    c[hw] = s;
+}

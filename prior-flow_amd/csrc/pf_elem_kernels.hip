@@ -1210,6 +1210,34 @@ int launch_lookup_bwd(const PfLookupBwdArgs& a, long total, void* stream) {
     return (int)hipGetLastError();
 }
 
+// forward_interpolate's scan: cell counts -> exclusive offsets, one 1024-thread workgroup per image (a contiguous run of cells
+// per thread, a Hillis-Steele scan of the run sums in LDS); pf_fi_scan_image is the host statement
+__global__ void __launch_bounds__(1024) pf_fi_scan_kernel(const PfFwdInterpArgs a) {
+    __shared__ int sums[1024];
+    const long hw = (long)a.h * a.w;
+    int* c = a.cell + blockIdx.x * (hw + 1);
+    const int tid = threadIdx.x;
+    const long per = (hw + 1023) / 1024;
+    const long lo = tid * per < hw ? tid * per : hw, hi = lo + per < hw ? lo + per : hw;
+    int s = 0;
+    for (long i = lo; i < hi; ++i) s += c[i];
+    sums[tid] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int t = tid >= d ? sums[tid - d] : 0;
+        __syncthreads();
+        sums[tid] += t;
+        __syncthreads();
+    }
+    int base = tid ? sums[tid - 1] : 0;
+    for (long i = lo; i < hi; ++i) { const int v = c[i]; c[i] = base; base += v; }
+    if (tid == 1023) c[hw] = sums[1023];
+}
+int launch_fi_scan(const PfFwdInterpArgs& a, void* stream) {
+    hipLaunchKernelGGL(pf_fi_scan_kernel, dim3((unsigned)a.B), dim3(1024), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 #define PF_LOOKUP_BWD_LAUNCH(a, total, stream) launch_lookup_bwd(a, total, stream)
@@ -1235,6 +1263,7 @@ int pf_lookup_feat_launch(const PfLookupFeatArgs& a, void* stream);
 #define PF_SEQ_LOSS_LAUNCH(a, stream) launch_seq_loss(a, stream)
 #define PF_SEQ_LOSS_BATCH_LAUNCH(t, stream) launch_seq_loss_batch(t, stream)
 #define PF_SUMSQ_LAUNCH(a, stream) launch_sumsq(a, stream)
+#define PF_FI_SCAN_LAUNCH(a, stream) launch_fi_scan(a, stream)
 #define PF_FLOW_OUT_LAUNCH(a, total, stream) launch_flow_out(a, total, stream)
 #define PF_NORM_ACT_LAUNCH(a, total, stream) launch_norm_act(a, total, stream)
 #define PF_STATS_LAUNCH launch_stats

@@ -58,6 +58,30 @@ class InputPadder:
         return x[..., top:rows, left:cols]
 
 
+def forward_interpolate(flow: torch.Tensor, wrap: bool = False, out: Optional[torch.Tensor] = None,
+                        scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """RAFT's warm start of a sequence (core/utils/utils.py:30-58) on the device: every pixel moves by its flow, the moved points
+    inside the frame (0 < x1 < w, 0 < y1 < h, strict) are kept, and every grid pixel takes the flow of the nearest kept point
+    (griddata 'nearest'; equally near points: the lowest source index).  wrap=True (ERP): x1 modulo w and wrapped x distances,
+    the model's own cyclic sampling.  An image without a kept point gives zeros (the reference's scipy raises).  flow: device
+    tensor [2,h,w] or [B,2,h,w]; returns fp32 of the same shape (into `out` when given).  pf_forward_interpolate is exact and
+    capturable; `scratch` (a device tensor of PfLib.forward_interpolate_scratch_bytes bytes) makes the call allocation-free."""
+    if not flow.is_cuda:
+        raise _lib.PfError("forward_interpolate runs on the device (pf_forward_interpolate); there is no CPU path")
+    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
+        raise _lib.PfError(f"forward_interpolate: flow {tuple(flow.shape)}, expected [2,h,w] or [B,2,h,w]")
+    f4 = flow.reshape((-1,) + tuple(flow.shape[-3:])).float().contiguous()
+    B, _, h, w = f4.shape
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(f4)
+    if scratch is None:
+        scratch = torch.empty(lib.forward_interpolate_scratch_bytes(B, h, w) // 4, dtype=torch.int32, device=flow.device)
+    with torch.cuda.device(flow.device):
+        lib.forward_interpolate(f4, out.view(f4.shape), scratch, wrap)
+    return out.view(flow.shape)
+
+
 def spherical_mask(H: int, W: int) -> np.ndarray:
     """cos(latitude) weights normalised to sum 1, as a numpy array (core/utils/spherical.py:11-17)."""
     n = torch.arange(0, H).view(-1, 1).repeat(1, W)

@@ -149,8 +149,10 @@ class PriOr_RAFT(nn.Module):
             del self._ws[old]
             for gk in [gk for gk in self._graphs if (gk[0], gk[1], gk[2], gk[4]) == old]:
                 del self._graphs[gk]      # a graph holds pointers into its workspace
-            for plan in (self._enc_plans or ()):
-                plan.release(old[1], old[2], (2 * old[0], 4 * old[0]))      # ... and into the encoders' activation buffers
+            # ... and into the encoders' activation buffers: cnet's of 2B images, fnet's of 4B (only those -- cnet's set of 4B
+            # images belongs to a resident batch of 2B, whose graph replays into it)
+            for plan, images in zip(self._enc_plans or (), (2, 4)):
+                plan.release(old[1], old[2], (images * old[0],))
         return ws
 
     def _encoder_plans(self):
