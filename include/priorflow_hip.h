@@ -69,6 +69,27 @@ int pf_prepare_frame(const float* image, const float* grid, float* out, int B, i
 int pf_forward_interpolate(const float* flow, float* out, void* scratch, long scratch_bytes, int B, int h, int w, int wrap,
                            void* stream);
 
+/* Forward-backward consistency of two opposite ERP flow fields, both directions in ONE launch (no host synchronisation).
+ * flow_fw (frame 0 -> 1, on frame 0's grid) and flow_bw (frame 1 -> 0, on frame 1's grid): NCHW [B,2,H,W], pixels.
+ * For a direction with flow f and opposite flow g, at pixel p = (x, y):
+ *   q = p + f;  g^ = g sampled at q with the model's cyclic sampler (x wrapped, y clamped, weights from the unclamped
+ *   fraction: core/utils/my_cycle_sample.py:31-60), the u component of the three non-anchor taps first brought to within W/2
+ *   of the anchor tap (as flo_rotate's seam handling, :82-97), v blended plainly;
+ *   round trip r = (u_clip(f_u + g^_u), f_v + g^_v), u_clip(t) = pymod(t + W/2, W) - W/2;
+ *   PF_FB_PLANE:  occluded <=> |r|^2 > alpha (|f|^2 + |g^|^2) + beta;
+ *   PF_FB_SPHERE: with d(a, b) the Haversine great-circle distance (R = 1) of two ERP points under the pixel -> (theta, phi)
+ *     map of pf_flow_metrics, y NOT clamped and the haversine clamped to [0, 1] (a point past a pole never gives NaN):
+ *     s_r = d(p, p + r), s_f = d(p, q), s_g = d(q, p + r);  occluded <=> s_r^2 > alpha (s_f^2 + s_g^2) + beta (2 pi / W)^2
+ *     (beta keeps its meaning of squared pixels at the equator).
+ *   A non-finite f or g^ gives occluded = 1 and r = 0.
+ * occ_fw / occ_bw: [B,H,W] bytes (1 = the round trip fails); res_fw / res_bw: [B,2,H,W] fp32 (r, pixels).
+ * PF_ERR_BAD_ARG: a NULL pointer, an output aliasing an input or another output, metric not PF_FB_*, alpha or beta negative
+ * or not finite.  PF_ERR_BAD_SHAPE: B < 1, H or W < 2, or H * W >= 2^30. */
+#define PF_FB_PLANE 0
+#define PF_FB_SPHERE 1
+int pf_fb_check(const float* flow_fw, const float* flow_bw, unsigned char* occ_fw, unsigned char* occ_bw, float* res_fw,
+                float* res_bw, int B, int H, int W, int metric, float alpha, float beta, void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

@@ -87,6 +87,7 @@ _SIGNATURES = {
     "pf_prepare_images": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp],
     "pf_prepare_frame": [_fp, _fp, _fp, _i, _i, _i, _fp],
     "pf_forward_interpolate": [_fp, _fp, _fp, C.c_long, _i, _i, _i, _i, _fp],
+    "pf_fb_check": [_fp] * 6 + [_i, _i, _i, _i, C.c_float, C.c_float, _fp],
     "pf_flow_prep": [_fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _i, _fp],
     "pf_flo_rotate": [_fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _i, _fp],
     "pf_corr_pyramid": [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp],
@@ -889,6 +890,24 @@ class PfLib:
             raise PfError("flow_metrics: pred and gt must have the same shape")
         self._rc(self._dll.pf_flow_metrics(_ptr(pred), _ptr(gt), _ptr(epe), _ptr(sd), int(cosine), B, H, W, self._stream(pred)),
                  "pf_flow_metrics")
+
+    FB_METRICS = {"plane": 0, "sphere": 1}          # PF_FB_PLANE / PF_FB_SPHERE
+
+    def fb_check(self, flow_fw, flow_bw, occ_fw, occ_bw, res_fw, res_bw, metric="sphere", alpha=0.01, beta=0.5):
+        """Forward-backward consistency of two opposite flows [B,2,H,W], both directions in one launch: occ_* uint8 [B,H,W]
+        (1 = the round trip fails), res_* fp32 [B,2,H,W] (the round trip, pixels).  metric: "sphere" | "plane"."""
+        self._chk(flow_fw, flow_bw, res_fw, res_bw)
+        if metric not in self.FB_METRICS:
+            raise PfError(f"fb_check: metric {metric!r}, expected 'sphere' or 'plane'")
+        if flow_fw.dim() != 4 or flow_fw.shape[1] != 2 or any(t.shape != flow_fw.shape for t in (flow_bw, res_fw, res_bw)):
+            raise PfError("fb_check: the flows and residuals must be four [B,2,H,W] tensors of one shape")
+        B, _, H, W = flow_fw.shape
+        for o in (occ_fw, occ_bw):
+            if o.dtype != torch.uint8 or tuple(o.shape) != (B, H, W) or not o.is_contiguous() or (self.require_cuda and not o.is_cuda):
+                raise PfError("fb_check: the masks must be contiguous uint8 [B,H,W] device tensors")
+        self._rc(self._dll.pf_fb_check(_ptr(flow_fw), _ptr(flow_bw), _ptr(occ_fw), _ptr(occ_bw), _ptr(res_fw), _ptr(res_bw),
+                                       B, H, W, self.FB_METRICS[metric], float(alpha), float(beta), self._stream(flow_fw)),
+                 "pf_fb_check")
 
     def region_sums(self, epe, sd, weight, bits, nregions, partials):
         """epe, sd: [B,H,W]; weight: [H*W] or None; bits: uint8 [H*W]; partials: float64 [B,nblk,nregions,3]."""

@@ -416,6 +416,26 @@ extern "C" int pf_flow_metrics(const float* pred, const float* gt, float* epe, f
     return PF_LAUNCH(flow_metrics, a, (long)B * H * W, stream);
 }
 
+// forward-backward check: the device build defines PF_FB_CHECK_LAUNCH (four pixels per thread where alignment allows)
+#ifndef PF_FB_CHECK_LAUNCH
+#define PF_FB_CHECK_LAUNCH(a, total, stream) PF_LAUNCH(fb_check, a, total, stream)
+#endif
+extern "C" int pf_fb_check(const float* flow_fw, const float* flow_bw, unsigned char* occ_fw, unsigned char* occ_bw, float* res_fw,
+                           float* res_bw, int B, int H, int W, int metric, float alpha, float beta, void* stream) {
+    PF_REQUIRE(flow_fw && flow_bw && occ_fw && occ_bw && res_fw && res_bw);
+    PF_REQUIRE(flow_fw != flow_bw && res_fw != res_bw && occ_fw != occ_bw);
+    PF_REQUIRE(res_fw != flow_fw && res_fw != flow_bw && res_bw != flow_fw && res_bw != flow_bw);
+    PF_REQUIRE((const void*)occ_fw != flow_fw && (const void*)occ_fw != flow_bw && (const void*)occ_bw != flow_fw &&
+               (const void*)occ_bw != flow_bw && (void*)occ_fw != res_fw && (void*)occ_fw != res_bw &&
+               (void*)occ_bw != res_fw && (void*)occ_bw != res_bw);
+    PF_REQUIRE(metric == PF_FB_PLANE || metric == PF_FB_SPHERE);
+    PF_REQUIRE(alpha >= 0.f && alpha <= 3.0e38f && beta >= 0.f && beta <= 3.0e38f);       // (a NaN fails both comparisons)
+    PF_REQUIRE_SHAPE(B > 0 && H > 1 && W > 1 && (long)H * W < (1L << 30));
+    PfFbCheckArgs a; a.fw = flow_fw; a.bw = flow_bw; a.occ_fw = occ_fw; a.occ_bw = occ_bw; a.res_fw = res_fw; a.res_bw = res_bw;
+    a.B = B; a.H = H; a.W = W; a.metric = metric; a.alpha = alpha; a.beta = beta;
+    return PF_FB_CHECK_LAUNCH(a, 2L * B * H * W, stream);
+}
+
 extern "C" int pf_region_sums(const float* epe, const float* sd, const float* weight, const unsigned char* bits,
                               int nregions, double* partials, int nblk, int B, int N, void* stream) {
     PF_REQUIRE(epe && sd && bits && partials);

@@ -1313,6 +1313,76 @@ PF_HD void pf_flow_metrics_elem(long idx, const PfFlowMetricsArgs& a) {   // idx
     }
 }
 
+// ----------------------------------------------------------------------------------------------
+// Forward-backward consistency of two opposite ERP flows (include/priorflow_hip.h: pf_fb_check).
+// pf_fb_pixel is the whole statement for one pixel of one direction; pf_fb_check_elem wraps it per pixel, the device's
+// 4-pixels-per-thread kernel (pf_elem_kernels.hip) calls the same function, so both forms give the same bits.
+// ----------------------------------------------------------------------------------------------
+struct PfFbCheckArgs {
+    const float* fw; const float* bw;            // [B,2,H,W]
+    unsigned char* occ_fw; unsigned char* occ_bw;   // [B,H,W]
+    float* res_fw; float* res_bw;                // [B,2,H,W]
+    int B, H, W, metric; float alpha, beta;
+};
+struct PfFbOut { float ru, rv; unsigned char occ; };
+PF_HD bool pf_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
+PF_HD float pf_fb_phi(float y, int H) { return (0.5f - (y + 0.5f) / (float)H) * 3.14159265358979323846f; }
+// Haversine distance of two ERP points from the cosines of their latitudes and their PIXEL difference (dx, dy): the angle
+// differences are formed from the (small) pixel differences, not from two large angles; the haversine is clamped to [0, 1]
+// (past a pole the product of the cosines is negative)
+PF_HD float pf_fb_dist(float cos_a, float cos_b, float dx, float dy, int H, int W) {
+    const float pi = 3.14159265358979323846f;
+    const float dth = (dx / (float)W) * (2.f * pi), dph = (dy / (float)H) * pi;
+    float hv = pf_haversine(dph) + (cos_a * cos_b) * pf_haversine(dth);
+    hv = hv < 0.f ? 0.f : (hv > 1.f ? 1.f : hv);
+    return 2.f * asinf(sqrtf(hv));
+}
+// one pixel (x, y) of image b, direction dir (0: f = forward flow, g = backward; 1: the other way round), f = (fu, fv) there
+PF_HD PfFbOut pf_fb_pixel(const PfFbCheckArgs& a, int dir, long b, int y, int x, float fu, float fv) {
+    const long N = (long)a.H * a.W;
+    const float Wf = (float)a.W;
+    const float* g0 = (dir ? a.fw : a.bw) + b * 2 * N;
+    const float* g1 = g0 + N;
+    const float qy = (float)y + fv;
+    const PfWrapTaps t = pf_wraptaps((float)x + fu, qy, a.H, a.W);        // indices always inside the map (NaN / huge included)
+    const float a0 = g0[t.ia];
+    const float gu = pf_wrapmix(t, a0, pf_unwrap_m(a0, g0[t.ib], Wf), pf_unwrap_m(a0, g0[t.ic], Wf), pf_unwrap_m(a0, g0[t.id], Wf));
+    const float gv = pf_wrapmix(t, g1[t.ia], g1[t.ib], g1[t.ic], g1[t.id]);
+    PfFbOut o;
+    o.ru = pf_pymod((fu + gu) + Wf * 0.5f, Wf) - Wf * 0.5f;              // u_clip
+    o.rv = fv + gv;
+    if (!(pf_finite(fu) && pf_finite(fv) && pf_finite(gu) && pf_finite(gv) && pf_finite(o.ru) && pf_finite(o.rv))) {
+        o.ru = 0.f; o.rv = 0.f; o.occ = 1;
+        return o;
+    }
+    float lhs, rhs;
+    if (a.metric == 0) {        // PF_FB_PLANE
+        lhs = o.ru * o.ru + o.rv * o.rv;
+        rhs = a.alpha * ((fu * fu + fv * fv) + (gu * gu + gv * gv)) + a.beta;
+    } else {                    // PF_FB_SPHERE: the sides of the spherical triangle p, q = p + f, p + r  (q -> p + r moves by g^)
+        const float cp = cosf(pf_fb_phi((float)y, a.H)), cq = cosf(pf_fb_phi(qy, a.H)), cr = cosf(pf_fb_phi((float)y + o.rv, a.H));
+        const float sr = pf_fb_dist(cp, cr, o.ru, o.rv, a.H, a.W);
+        const float sf = pf_fb_dist(cp, cq, fu, fv, a.H, a.W);
+        const float sg = pf_fb_dist(cq, cr, gu, gv, a.H, a.W);
+        const float px = 6.28318530717958647692f / Wf;                  // one pixel at the equator
+        lhs = sr * sr;
+        rhs = a.alpha * (sf * sf + sg * sg) + a.beta * (px * px);
+    }
+    o.occ = lhs > rhs ? 1 : 0;
+    return o;
+}
+PF_HD void pf_fb_check_elem(long idx, const PfFbCheckArgs& a) {   // idx over 2*B*H*W: direction, image, pixel
+    const long N = (long)a.H * a.W, BN = (long)a.B * N;
+    const int dir = (int)(idx / BN);
+    const long r = idx % BN, b = r / N, n = r % N;
+    const float* f = (dir ? a.bw : a.fw) + b * 2 * N;
+    const int y = (int)n / a.W;                  // H * W < 2^30 (checked by the entry point): a 32-bit division
+    const PfFbOut o = pf_fb_pixel(a, dir, b, y, (int)n - y * a.W, f[n], f[N + n]);
+    (dir ? a.occ_bw : a.occ_fw)[r] = o.occ;
+    float* res = (dir ? a.res_bw : a.res_fw) + b * 2 * N;
+    res[n] = o.ru; res[N + n] = o.rv;
+}
+
 // Region sums (evaluate.py:246-275): pixel n belongs to region r when bit r of bits[n] is set.
 // partials[((b*nblk + k)*R + r)*3 + {0,1,2}] = sum epe, sum sd, sum sd*weight over block k's pixels.
 struct PfRegionSumArgs {

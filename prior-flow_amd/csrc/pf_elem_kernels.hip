@@ -1238,8 +1238,45 @@ int launch_fi_scan(const PfFwdInterpArgs& a, void* stream) {
     return (int)hipGetLastError();
 }
 
+// Forward-backward check, four consecutive pixels of a row per thread (W % 4 == 0, 16-byte aligned maps): the flow is read and
+// the residual written as 16-byte vectors, the four mask bytes as one dword, both directions in one grid.  The 4-tap gathers of
+// the opposite flow stay scalar loads (their columns wrap at the seam).  pf_fb_pixel is the element form's statement.
+__global__ void __launch_bounds__(kBlock) pf_fb_check_vec4(const PfFbCheckArgs a, const long total4) {
+    const long N = (long)a.H * a.W, BN = (long)a.B * N;
+    long i = (long)blockIdx.x * kBlock + threadIdx.x;
+    const long stride = (long)gridDim.x * kBlock;
+    for (; i < total4; i += stride) {
+        const long idx = i * 4;
+        const int dir = (int)(idx / BN);
+        const long r = idx % BN, b = r / N, n = r % N;
+        const int y = (int)n / a.W, x = (int)n - y * a.W;            // H * W < 2^30: a 32-bit division
+        const float* f = (dir ? a.bw : a.fw) + b * 2 * N + n;
+        const float4 fu = *reinterpret_cast<const float4*>(f), fv = *reinterpret_cast<const float4*>(f + N);
+        const PfFbOut o0 = pf_fb_pixel(a, dir, b, y, x, fu.x, fv.x);
+        const PfFbOut o1 = pf_fb_pixel(a, dir, b, y, x + 1, fu.y, fv.y);
+        const PfFbOut o2 = pf_fb_pixel(a, dir, b, y, x + 2, fu.z, fv.z);
+        const PfFbOut o3 = pf_fb_pixel(a, dir, b, y, x + 3, fu.w, fv.w);
+        float* res = (dir ? a.res_bw : a.res_fw) + b * 2 * N + n;
+        *reinterpret_cast<float4*>(res) = make_float4(o0.ru, o1.ru, o2.ru, o3.ru);
+        *reinterpret_cast<float4*>(res + N) = make_float4(o0.rv, o1.rv, o2.rv, o3.rv);
+        *reinterpret_cast<unsigned*>((dir ? a.occ_bw : a.occ_fw) + r) =
+            (unsigned)o0.occ | ((unsigned)o1.occ << 8) | ((unsigned)o2.occ << 16) | ((unsigned)o3.occ << 24);
+    }
+}
+int launch_fb_check(const PfFbCheckArgs& a, long total, void* stream) {
+    const uintptr_t maps = (uintptr_t)a.fw | (uintptr_t)a.bw | (uintptr_t)a.res_fw | (uintptr_t)a.res_bw;
+    const bool vec = a.W % 4 == 0 && maps % 16 == 0 && ((uintptr_t)a.occ_fw | (uintptr_t)a.occ_bw) % 4 == 0;
+    if (!vec) return pf_launch_elem<PfFbCheckArgs, pf_fb_check_elem>(a, total, stream);
+    const long n4 = total / 4;
+    long blocks = (n4 + kBlock - 1) / kBlock;
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+    hipLaunchKernelGGL(pf_fb_check_vec4, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, n4);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
+#define PF_FB_CHECK_LAUNCH(a, total, stream) launch_fb_check(a, total, stream)
 #define PF_LOOKUP_BWD_LAUNCH(a, total, stream) launch_lookup_bwd(a, total, stream)
 #define PF_UPSAMPLE_BWD_LAUNCH(a, total, stream) launch_upsample_bwd(a, total, stream)
 #define PF_COMBINE_LAUNCH(a, total, stream) launch_combine(a, total, stream)
