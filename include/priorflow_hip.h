@@ -90,6 +90,59 @@ int pf_forward_interpolate(const float* flow, float* out, void* scratch, long sc
 int pf_fb_check(const float* flow_fw, const float* flow_bw, unsigned char* occ_fw, unsigned char* occ_bw, float* res_fw,
                 float* res_bw, int B, int H, int W, int metric, float alpha, float beta, void* stream);
 
+/* Order statistic on the device: out[b] = np.sort(x[b])[k] for each image of x [B, n] (fp32, NON-NEGATIVE values: a length),
+ * 0 <= k < n, bit for bit, equal values included; no host read, no allocation, capturable.  A radix select over the bit pattern
+ * (11 + 11 + 10 bits; LDS histograms, one integer atomic per non-empty bin and workgroup, so the result does not depend on the
+ * order of the adds): five launches.  +inf is an ordinary largest value.  NaN ranks last, as numpy sorts it; when rank k falls on
+ * a NaN the result is the largest value that is not NaN (0 when there is none).  Outside the contract: a value with the sign bit
+ * set counts as +0.  scratch: device memory of at least pf_order_stat_scratch_bytes(B, n) bytes, 4-byte aligned, overwritten.
+ * PF_ERR_BAD_ARG: a NULL pointer, x == out, k outside [0, n) or scratch_bytes too small.  PF_ERR_BAD_SHAPE: B < 1,
+ * B > PF_MAX_IMAGES (an image is one row of the launch grid), n < 1, n >= 2^31. */
+#define PF_MAX_IMAGES 65535
+long pf_order_stat_scratch_bytes(int B, long n);
+int pf_order_stat(const float* x, float* out, void* scratch, long scratch_bytes, int B, long n, long k, void* stream);
+
+/* Colour coding of flow fields (core/utils/flow_viz.py): flow NCHW [B,2,H,W] fp32 -> 8-bit image, per image of the batch.
+ *   PF_RENDER_OMNI  = omniflow_to_image (:144-215, clip_flow = None): len = great-circle length of the flow
+ *                     (calculate_veclen_spherical, core/utils/spherical.py:56-70; R = 1), clip = sort(len)[k],
+ *                     k = min(int(percentile * H * W), H * W - 1) computed in double (the reference: 0.95);
+ *   PF_RENDER_PLANE = flow_to_image (:117-141): len = |flow|, clip = max len (percentile ignored).
+ *   rad = min(len, clip) / (clip + 1e-5); a = atan2(-v, -u) / pi; fk = (a + 1) / 2 * 54 blends entries floor(fk) and floor(fk) + 1
+ *   (55 -> 0) of the 55-entry Middlebury wheel; col = 1 - rad (1 - blend) (rad > 1: 0.75 blend); byte = floor(255 col); all fp32.
+ * A pixel whose flow is not finite counts as NaN in the order statistic (pf_order_stat: it ranks last) and is written (0, 0, 0);
+ * every finite flow has a finite length (the haversine is clamped to 1: an antipodal end point never gives NaN) and is ranked.
+ * out: PF_LAYOUT_HWC [B,H,W,3] or PF_LAYOUT_CHW [B,3,H,W]; bgr = 1 reverses the channel order (convert_to_bgr).
+ * Five launches, no host read: zero the counts; len to scratch fused with the first select pass; two select passes; colourise
+ * (each workgroup makes the last choice of the select itself).  Four pixels of a row per thread when W % 4 == 0, flow and scratch
+ * are 16-byte aligned and out 4-byte aligned, one pixel per thread otherwise: the same per-pixel function, the same bytes.
+ * scratch: at least pf_flow_render_scratch_bytes(B, H, W) bytes, overwritten; afterwards it starts with len [B,H,W] fp32, followed
+ * by clip [B] fp32.  PF_ERR_BAD_ARG: a NULL pointer, flow == out, mode / layout / bgr not one of their values, percentile outside
+ * [0, 1] or scratch_bytes too small.  PF_ERR_BAD_SHAPE: B < 1, B > PF_MAX_IMAGES, H or W < 2, H * W >= 2^30. */
+#define PF_RENDER_OMNI 0
+#define PF_RENDER_PLANE 1
+#define PF_LAYOUT_HWC 0
+#define PF_LAYOUT_CHW 1
+long pf_flow_render_scratch_bytes(int B, int H, int W);
+int pf_flow_render(const float* flow, unsigned char* out, void* scratch, long scratch_bytes, int B, int H, int W, int mode,
+                   double percentile, int layout, int bgr, void* stream);
+
+/* my_cycle_warp (core/utils/my_cycle_sample.py:100-115): out[b,c,y,x] = x[b,c] sampled at (x + u, y + v), (u, v) = flo[b,:,y,x],
+ * with the model's cyclic sampler (x wrapped, y clamped, weights from the unclamped fraction; no seam un-wrapping).  x, out:
+ * [B,C,H,W] fp32, any C >= 1; flo: [B,2,H,W].  The taps of a pixel are computed once for its C channels.  ref (frame 1, [B,C,H,W])
+ * and err ([B,H,W]) are given together or both NULL: err = mean over c of |ref - out|, written by the same launch.  A flow that is
+ * not finite gives NaN in out (and err) at that pixel; every read stays inside the maps.
+ * PF_ERR_BAD_ARG: a NULL x / flo / out, an output aliasing an input or the other output, only one of ref / err.
+ * PF_ERR_BAD_SHAPE: B or C < 1, H or W < 2, H * W >= 2^30. */
+int pf_cycle_warp(const float* x, const float* flo, const float* ref, float* out, float* err, int B, int C, int H, int W,
+                  void* stream);
+
+/* out[b] = mean of x[b, :] over the elements with mask[b, n] == 0 (mask NULL: all of them; nothing counted: 0).  x: [B,N] fp32,
+ * mask: [B,N] bytes.  fp64 sums of at most 64 chunks per image, then one sum in chunk order: deterministic, two launches, no
+ * host read.  scratch: at least 1024 * B bytes, 8-byte aligned.  PF_ERR_BAD_ARG: a NULL x / out / scratch, out == x, scratch
+ * misaligned or too small.  PF_ERR_BAD_SHAPE: B < 1, B > PF_MAX_IMAGES, N < 1, N >= 2^30. */
+int pf_masked_mean(const float* x, const unsigned char* mask, float* out, void* scratch, long scratch_bytes, int B, int N,
+                   void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

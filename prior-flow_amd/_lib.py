@@ -154,6 +154,12 @@ _SIGNATURES = {
     "pf_adamw_step_dev": [_fp, _fp, _fp, _fp, C.c_long, C.c_float, C.c_float, C.c_float, _fp, _fp],
     "pf_flow_metrics": [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp],
     "pf_region_sums": [_fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _fp],
+    "pf_order_stat_scratch_bytes": [_i, C.c_long],
+    "pf_order_stat": [_fp, _fp, _fp, C.c_long, _i, C.c_long, C.c_long, _fp],
+    "pf_flow_render_scratch_bytes": [_i, _i, _i],
+    "pf_flow_render": [_fp, _fp, _fp, C.c_long, _i, _i, _i, _i, C.c_double, _i, _i, _fp],
+    "pf_cycle_warp": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp],
+    "pf_masked_mean": [_fp, _fp, _fp, _fp, C.c_long, _i, _i, _fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
 
@@ -237,7 +243,7 @@ class PfLib:
                     continue
                 raise PfError(f"{path} does not export {name}")
             fn.argtypes = args
-            fn.restype = C.c_long if name.endswith("_ws_floats") else _i
+            fn.restype = C.c_long if name.endswith(("_ws_floats", "_scratch_bytes")) else _i
 
     # ---- helpers -----------------------------------------------------------------------------
     def version(self) -> str:
@@ -922,6 +928,83 @@ class PfLib:
         self._rc(self._dll.pf_region_sums(_ptr(epe), _ptr(sd), _ptr(weight), C.c_void_p(bits.data_ptr()), nregions,
                                           C.c_void_p(partials.data_ptr()), partials.shape[1], B, N,
                                           self._stream(epe)), "pf_region_sums")
+
+    # ---- flow rendering ------------------------------------------------
+    RENDER_MODES = {"omni": 0, "plane": 1}          # PF_RENDER_OMNI / PF_RENDER_PLANE
+    RENDER_LAYOUTS = {"hwc": 0, "chw": 1}           # PF_LAYOUT_HWC / PF_LAYOUT_CHW
+
+    def _chk_bytes(self, t, what, dtype=None):
+        """A contiguous device buffer handed over as raw memory (scratch, byte images, masks)."""
+        if not t.is_contiguous() or (dtype is not None and t.dtype != dtype):
+            raise PfError(f"{what}: expected a contiguous {dtype or 'device'} tensor, got {t.dtype} contiguous={t.is_contiguous()}")
+        if self.require_cuda and not t.is_cuda:
+            raise PfError(f"{what}: the HIP path needs tensors on a cuda (ROCm) device; there is no CPU fallback")
+
+    def order_stat_scratch_bytes(self, B: int, n: int) -> int:
+        r = self._dll.pf_order_stat_scratch_bytes(B, n)
+        self._rc(min(r, 0), "pf_order_stat_scratch_bytes")
+        return r
+
+    def order_stat(self, x, k: int, out, scratch):
+        """out[b] = sort(x[b])[k] of a non-negative fp32 [B, n] map, exact (pf_order_stat); scratch: order_stat_scratch_bytes."""
+        self._chk(x, out)
+        self._chk_bytes(scratch, "order_stat: scratch")
+        if x.dim() != 2 or out.numel() != x.shape[0]:
+            raise PfError(f"order_stat: x {tuple(x.shape)} / out {tuple(out.shape)}: expected [B, n] and [B]")
+        self._rc(self._dll.pf_order_stat(_ptr(x), _ptr(out), _ptr(scratch), scratch.numel() * scratch.element_size(),
+                                         x.shape[0], x.shape[1], int(k), self._stream(x)), "pf_order_stat")
+        return out
+
+    def flow_render_scratch_bytes(self, B: int, H: int, W: int) -> int:
+        r = self._dll.pf_flow_render_scratch_bytes(B, H, W)
+        self._rc(min(r, 0), "pf_flow_render_scratch_bytes")
+        return r
+
+    def flow_render(self, flow, out, scratch, mode="omni", percentile=0.95, layout="hwc", bgr=False):
+        """Colour coding of flows [B,2,H,W] into a uint8 image [B,H,W,3] ("hwc") or [B,3,H,W] ("chw") (pf_flow_render)."""
+        self._chk(flow)
+        if mode not in self.RENDER_MODES or layout not in self.RENDER_LAYOUTS:
+            raise PfError(f"flow_render: mode {mode!r} / layout {layout!r}, expected 'omni' | 'plane' and 'hwc' | 'chw'")
+        if flow.dim() != 4 or flow.shape[1] != 2:
+            raise PfError(f"flow_render: flow {tuple(flow.shape)}, expected [B,2,H,W]")
+        B, _, H, W = flow.shape
+        self._chk_bytes(out, "flow_render: out", torch.uint8)
+        self._chk_bytes(scratch, "flow_render: scratch")
+        if tuple(out.shape) != ((B, H, W, 3) if layout == "hwc" else (B, 3, H, W)):
+            raise PfError(f"flow_render: out {tuple(out.shape)} does not fit flow {tuple(flow.shape)} in layout {layout!r}")
+        self._rc(self._dll.pf_flow_render(_ptr(flow), _ptr(out), _ptr(scratch), scratch.numel() * scratch.element_size(), B, H, W,
+                                          self.RENDER_MODES[mode], float(percentile), self.RENDER_LAYOUTS[layout], int(bool(bgr)),
+                                          self._stream(flow)), "pf_flow_render")
+        return out
+
+    def cycle_warp(self, x, flo, out, ref=None, err=None):
+        """my_cycle_warp: out = x [B,C,H,W] sampled at pixel + flo [B,2,H,W]; with ref and err [B,H,W]: err = mean_c |ref - out|."""
+        self._chk(x, flo, out, ref, err)
+        if x.dim() != 4 or flo.dim() != 4 or flo.shape[1] != 2 or flo.shape[0] != x.shape[0] or flo.shape[2:] != x.shape[2:] \
+                or out.shape != x.shape or (ref is not None and ref.shape != x.shape):
+            raise PfError(f"cycle_warp: x {tuple(x.shape)} / flo {tuple(flo.shape)} / out {tuple(out.shape)} do not fit")
+        B, Cc, H, W = x.shape
+        if (ref is None) != (err is None) or (err is not None and tuple(err.shape) != (B, H, W)):
+            raise PfError("cycle_warp: ref [B,C,H,W] and err [B,H,W] go together")
+        self._rc(self._dll.pf_cycle_warp(_ptr(x), _ptr(flo), _ptr(ref), _ptr(out), _ptr(err), B, Cc, H, W, self._stream(x)),
+                 "pf_cycle_warp")
+        return out
+
+    def masked_mean(self, x, mask, out, scratch):
+        """out[b] = mean of x[b] over mask[b] == 0 (mask None: everything); scratch: >= 1024 * B bytes."""
+        self._chk(x, out)
+        self._chk_bytes(scratch, "masked_mean: scratch")
+        B = x.shape[0]
+        N = x[0].numel()
+        if mask is not None:
+            self._chk_bytes(mask, "masked_mean: mask", torch.uint8)
+            if mask.numel() != B * N:
+                raise PfError("masked_mean: mask and x differ in size")
+        if out.numel() != B:
+            raise PfError("masked_mean: out must hold one value per image")
+        self._rc(self._dll.pf_masked_mean(_ptr(x), _ptr(mask), _ptr(out), _ptr(scratch), scratch.numel() * scratch.element_size(),
+                                          B, N, self._stream(x)), "pf_masked_mean")
+        return out
 
     def to_nchw(self, x, off_in, c, out):
         self._chk(x, out)

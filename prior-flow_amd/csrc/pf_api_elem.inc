@@ -710,3 +710,114 @@ extern "C" int pf_motion_prep_f16(const float* c1a, const float* c1b, const floa
 
 extern "C" int pf_dccl_combine_conv1x1_f16(const pf_combine_conv_desc*, int, int, int, int, void*) { return PF_ERR_BAD_SHAPE; }
 #endif
+
+// ---- flow rendering (DESIGN.md section 13): order statistic, colour coding, cyclic warp ----------------------------------------
+#if !defined(__HIPCC__)
+// Host build (tests/emu): a select pass as its host statement (the choice of the previous pass per image, then the counts element
+// by element); the device build defines these macros as the workgroup kernels of pf_elem_kernels.hip and never falls back to this.
+static int pf_os_pass_host(PfOrderStatArgs a, int pass, void* stream) {
+    a.pass = pass;
+    if (pass > 0)
+        for (int b = 0; b < a.B; ++b) pf_os_select_image(a, b, pass);
+    return PF_LAUNCH(os_hist, a, (long)a.B * a.n, stream);
+}
+static int pf_os_final_host(const PfOrderStatArgs& a, void*) {
+    for (int b = 0; b < a.B; ++b) pf_os_select_image(a, b, 3);
+    return PF_OK;
+}
+static int pf_render_len_host(const PfOrderStatArgs& o, const PfRenderArgs& r, void* stream) {
+    const int rc = PF_LAUNCH(render_len, r, (long)r.B * r.H * r.W, stream);
+    return rc == PF_OK ? pf_os_pass_host(o, 0, stream) : rc;
+}
+static int pf_render_color_host(const PfOrderStatArgs& o, const PfRenderArgs& r, void* stream) {
+    const int rc = pf_os_final_host(o, stream);
+    return rc == PF_OK ? PF_LAUNCH(render_color, r, (long)r.B * r.H * r.W, stream) : rc;
+}
+static int pf_masked_mean_host(const PfMaskedMeanArgs& a, void*) {
+    const int chunk = (a.N + a.nblk - 1) / a.nblk;
+    for (int b = 0; b < a.B; ++b)
+        for (int k = 0; k < a.nblk; ++k) {
+            double s = 0.0, c = 0.0;
+            for (int n = k * chunk; n < (k + 1) * chunk && n < a.N; ++n)
+                if (!a.mask || a.mask[(long)b * a.N + n] == 0) { s += (double)a.x[(long)b * a.N + n]; c += 1.0; }
+            a.partials[((long)b * a.nblk + k) * 2] = s; a.partials[((long)b * a.nblk + k) * 2 + 1] = c;
+        }
+    return PF_OK;
+}
+#define PF_OS_PASS_LAUNCH(a, pass, stream) pf_os_pass_host(a, pass, stream)
+#define PF_OS_FINAL_LAUNCH(a, stream) pf_os_final_host(a, stream)
+#define PF_RENDER_LEN_LAUNCH(o, r, stream) pf_render_len_host(o, r, stream)
+#define PF_RENDER_COLOR_LAUNCH(o, r, stream) pf_render_color_host(o, r, stream)
+#define PF_MASKED_MEAN_LAUNCH(a, stream) pf_masked_mean_host(a, stream)
+#endif
+
+extern "C" long pf_order_stat_scratch_bytes(int B, long n) {
+    if (B <= 0 || B > PF_MAX_IMAGES || n <= 0 || n >= (1L << 31)) return PF_ERR_BAD_SHAPE;
+    return 4L * B * (PF_OS_HIST + 4);
+}
+
+static inline void pf_os_fill(PfOrderStatArgs& a, const float* x, float* out, void* scratch, int B, long n, long k) {
+    a.x = x; a.out = out; a.hist = (unsigned*)scratch; a.state = a.hist + (long)B * PF_OS_HIST;
+    a.n = n; a.k = k; a.B = B; a.pass = 0;
+}
+
+extern "C" int pf_order_stat(const float* x, float* out, void* scratch, long scratch_bytes, int B, long n, long k, void* stream) {
+    PF_REQUIRE(x && out && scratch && (const void*)x != (const void*)out);
+    PF_REQUIRE_SHAPE(B > 0 && B <= PF_MAX_IMAGES && n > 0 && n < (1L << 31));
+    PF_REQUIRE(k >= 0 && k < n && scratch_bytes >= pf_order_stat_scratch_bytes(B, n) && ((unsigned long)scratch & 3ul) == 0);
+    PfOrderStatArgs a; pf_os_fill(a, x, out, scratch, B, n, k);
+    int rc = PF_LAUNCH(os_zero, a, (long)B * (PF_OS_HIST + 4), stream);
+    for (int p = 0; p < 3 && rc == PF_OK; ++p) rc = PF_OS_PASS_LAUNCH(a, p, stream);
+    if (rc == PF_OK) rc = PF_OS_FINAL_LAUNCH(a, stream);
+    return rc;
+}
+
+extern "C" long pf_flow_render_scratch_bytes(int B, int H, int W) {
+    if (B <= 0 || B > PF_MAX_IMAGES || H <= 1 || W <= 1 || (long)H * W >= (1L << 30)) return PF_ERR_BAD_SHAPE;
+    return 4L * B * H * W + 4L * B + pf_order_stat_scratch_bytes(B, (long)H * W);
+}
+
+extern "C" int pf_flow_render(const float* flow, unsigned char* out, void* scratch, long scratch_bytes, int B, int H, int W,
+                              int mode, double percentile, int layout, int bgr, void* stream) {
+    PF_REQUIRE(flow && out && scratch && (const void*)flow != (const void*)out);
+    PF_REQUIRE(mode == PF_RENDER_OMNI || mode == PF_RENDER_PLANE);
+    PF_REQUIRE(layout == PF_LAYOUT_HWC || layout == PF_LAYOUT_CHW);
+    PF_REQUIRE(bgr == 0 || bgr == 1);
+    PF_REQUIRE(percentile >= 0.0 && percentile <= 1.0);                    // (a NaN fails both comparisons)
+    PF_REQUIRE_SHAPE(B > 0 && B <= PF_MAX_IMAGES && H > 1 && W > 1 && (long)H * W < (1L << 30));
+    PF_REQUIRE(scratch_bytes >= pf_flow_render_scratch_bytes(B, H, W) && ((unsigned long)scratch & 3ul) == 0);
+    const long N = (long)H * W;
+    long k = mode == PF_RENDER_PLANE ? N - 1 : (long)(percentile * (double)N);
+    if (k > N - 1) k = N - 1;
+    PfRenderArgs r; r.flow = flow; r.len = (float*)scratch; r.out = out; r.B = B; r.H = H; r.W = W;
+    r.mode = mode; r.planar = layout == PF_LAYOUT_CHW; r.bgr = bgr;
+    float* clip = r.len + (long)B * N;
+    r.clip = clip;
+    PfOrderStatArgs a; pf_os_fill(a, r.len, clip, clip + B, B, N, k);
+    int rc = PF_LAUNCH(os_zero, a, (long)B * (PF_OS_HIST + 4), stream);
+    if (rc == PF_OK) rc = PF_RENDER_LEN_LAUNCH(a, r, stream);
+    if (rc == PF_OK) rc = PF_OS_PASS_LAUNCH(a, 1, stream);
+    if (rc == PF_OK) rc = PF_OS_PASS_LAUNCH(a, 2, stream);
+    if (rc == PF_OK) rc = PF_RENDER_COLOR_LAUNCH(a, r, stream);
+    return rc;
+}
+
+extern "C" int pf_cycle_warp(const float* x, const float* flo, const float* ref, float* out, float* err, int B, int C, int H,
+                             int W, void* stream) {
+    PF_REQUIRE(x && flo && out && out != x && out != flo && out != ref);
+    PF_REQUIRE((err != nullptr) == (ref != nullptr) && err != out && (!err || (err != x && err != flo && err != ref)));
+    PF_REQUIRE_SHAPE(B > 0 && C > 0 && H > 1 && W > 1 && (long)H * W < (1L << 30));
+    PfCycleWarpArgs a; a.x = x; a.flo = flo; a.ref = ref; a.out = out; a.err = err; a.B = B; a.C = C; a.H = H; a.W = W;
+    return PF_LAUNCH(cycle_warp, a, (long)B * H * W, stream);
+}
+
+extern "C" int pf_masked_mean(const float* x, const unsigned char* mask, float* out, void* scratch, long scratch_bytes, int B,
+                              int N, void* stream) {
+    PF_REQUIRE(x && out && scratch && out != x);
+    PF_REQUIRE_SHAPE(B > 0 && B <= PF_MAX_IMAGES && N > 0 && N < (1 << 30));
+    PF_REQUIRE(scratch_bytes >= 16L * B * PF_MM_BLOCKS && ((unsigned long)scratch & 7ul) == 0);
+    PfMaskedMeanArgs a; a.x = x; a.mask = mask; a.partials = (double*)scratch; a.out = out; a.B = B; a.N = N;
+    a.nblk = N < PF_MM_BLOCKS * 256 ? (N + 255) / 256 : PF_MM_BLOCKS;
+    const int rc = PF_MASKED_MEAN_LAUNCH(a, stream);
+    return rc == PF_OK ? PF_LAUNCH(masked_mean_final, a, (long)B, stream) : rc;
+}

@@ -1719,3 +1719,169 @@ PF_HD void pf_fi_scan_image(const PfFwdInterpArgs& a, int b) {
     for (long i = 0; i < hw; ++i) { const int v = c[i]; c[i] = s; s += v; }
     c[hw] = s;
 }
+
+// ----------------------------------------------------------------------------------------------
+// Order statistic of a non-negative map (include/priorflow_hip.h: pf_order_stat): out[b] = np.sort(x[b])[k],
+// bit for bit, by a radix select over the bit pattern in three passes of 11 + 11 + 10 bits.  Only integer counts are summed, so
+// the result does not depend on the order of the adds.  Key of a value: its bit pattern; NaN -> 0xFFFFFFFF (ranks last, alone in
+// bin 2047 of the first pass: finite values and +inf have a clear sign bit, so they end at bin 1020); a set sign bit -> 0.
+//   hist:  [B][2048 + 2048 + 1024] counts of the three passes (zeroed by the first launch)
+//   state: [B][2][2] (prefix, remaining rank) chosen from passes 0 and 1
+// Pass p > 0 first picks the bin of pass p - 1 that holds the rank (pf_os_select_image; on the device every workgroup repeats
+// that scan, pf_elem_kernels.hip), then counts the digit of the elements whose higher bits equal the prefix.
+// ----------------------------------------------------------------------------------------------
+#define PF_OS_HIST 5120
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PF_ATOMIC_INC_U32(ptr) atomicAdd((ptr), 1u)
+#else
+#define PF_ATOMIC_INC_U32(ptr) __atomic_fetch_add((ptr), 1u, __ATOMIC_RELAXED)
+#endif
+struct PfOrderStatArgs { const float* x; unsigned* hist; unsigned* state; float* out; long n, k; int B, pass; };
+PF_HD unsigned pf_os_key(float v) {
+    union { float f; unsigned u; } c; c.f = v;
+    if ((c.u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    return (c.u >> 31) ? 0u : c.u;
+}
+PF_HD int pf_os_nbins(int pass) { return pass == 2 ? 1024 : 2048; }
+PF_HD int pf_os_hoff(int pass) { return pass * 2048; }
+PF_HD unsigned pf_os_digit(unsigned key, int pass) { return pass == 0 ? key >> 21 : (pass == 1 ? (key >> 10) & 0x7ffu : key & 0x3ffu); }
+PF_HD bool pf_os_match(unsigned key, int pass, unsigned prefix) {
+    return pass == 0 ? true : (pass == 1 ? (key >> 21) == prefix : (key >> 10) == prefix);
+}
+// rank looked for in the counts of pass 0: k, or the last value that is not NaN when k falls on a NaN
+PF_HD unsigned pf_os_rank0(long n, long k, unsigned n_nan) {
+    const long nn = n - (long)n_nan;
+    return (unsigned)(nn <= 0 ? 0 : (k < nn ? k : nn - 1));
+}
+PF_HD unsigned pf_os_prefix(unsigned prefix, unsigned bin, int p) { return p == 1 ? bin : ((prefix << (p == 2 ? 11 : 10)) | bin); }
+PF_HD float pf_os_value(unsigned key) { union { float f; unsigned u; } c; c.u = key; return c.f; }
+// the choice made after pass p - 1 (p = 1, 2: into state; p = 3: the result), one image; the host statement of the device's scan.
+// The first bin whose running count exceeds the rank; no such bin (an image of NaNs only) -> bin 0, which later passes find empty.
+PF_HD void pf_os_select_image(const PfOrderStatArgs& a, int b, int p) {
+    const unsigned* h = a.hist + (long)b * PF_OS_HIST + pf_os_hoff(p - 1);
+    const int nb = p == 1 ? 2047 : pf_os_nbins(p - 1);                   // pass 0: the NaN bin is left out
+    const unsigned prefix = p == 1 ? 0u : a.state[b * 4 + (p - 2) * 2];
+    const unsigned rank = p == 1 ? pf_os_rank0(a.n, a.k, h[2047]) : a.state[b * 4 + (p - 2) * 2 + 1];
+    unsigned cum = 0, bin = 0, rest = 0;
+    for (int j = 0; j < nb; ++j) {
+        if (cum + h[j] > rank) { bin = (unsigned)j; rest = rank - cum; break; }
+        cum += h[j];
+    }
+    const unsigned np = pf_os_prefix(prefix, bin, p);
+    if (p < 3) { a.state[b * 4 + (p - 1) * 2] = np; a.state[b * 4 + (p - 1) * 2 + 1] = rest; }
+    else a.out[b] = pf_os_value(np);
+}
+PF_HD void pf_os_zero_elem(long idx, const PfOrderStatArgs& a) { a.hist[idx] = 0u; }      // idx over B*(PF_OS_HIST + 4): hist, then state
+PF_HD void pf_os_hist_elem(long idx, const PfOrderStatArgs& a) {                           // idx over B*n (host statement of a pass)
+    const long b = idx / a.n;
+    const unsigned key = pf_os_key(a.x[idx]);
+    const unsigned prefix = a.pass ? a.state[b * 4 + (a.pass - 1) * 2] : 0u;
+    if (pf_os_match(key, a.pass, prefix)) PF_ATOMIC_INC_U32(a.hist + b * PF_OS_HIST + pf_os_hoff(a.pass) + pf_os_digit(key, a.pass));
+}
+
+// ----------------------------------------------------------------------------------------------
+// Colour coding of a flow field (include/priorflow_hip.h: pf_flow_render; core/utils/flow_viz.py:28-215).
+//   PF_RENDER_OMNI  (omniflow_to_image): len = great-circle length of the flow (calculate_veclen_spherical, core/utils/spherical.py:
+//                   56-70: pf_flow_metrics' haversine distance from the pixel to its end point), clip = the percentile of len
+//   PF_RENDER_PLANE (flow_to_image):     len = |flow|, clip = its maximum
+// rad = min(len, clip) / (clip + 1e-5); a = atan2(-v, -u) / pi picks and blends two entries of the 55-entry Middlebury wheel;
+// col = 1 - rad (1 - blend) (rad > 1: 0.75 blend, which the epsilon keeps unreachable); byte = floor(255 col).  All fp32.
+// A pixel whose flow is not finite has len = NaN (it ranks last in the percentile) and is written as (0, 0, 0).
+// ----------------------------------------------------------------------------------------------
+struct PfRenderArgs { const float* flow; float* len; const float* clip; unsigned char* out; int B, H, W, mode, planar, bgr; };
+struct PfRgb { unsigned char c[3]; };
+PF_HD unsigned char pf_wheel(int k, int i) {          // make_colorwheel (flow_viz.py:28-75): RY 15, YG 6, GC 4, CB 11, BM 13, MR 6
+    static const unsigned char wheel[55 * 3] = {
+        255,0,0,  255,17,0,  255,34,0,  255,51,0,  255,68,0,
+        255,85,0,  255,102,0,  255,119,0,  255,136,0,  255,153,0,
+        255,170,0,  255,187,0,  255,204,0,  255,221,0,  255,238,0,
+        255,255,0,  213,255,0,  170,255,0,  128,255,0,  85,255,0,
+        43,255,0,  0,255,0,  0,255,63,  0,255,127,  0,255,191,
+        0,255,255,  0,232,255,  0,209,255,  0,186,255,  0,163,255,
+        0,140,255,  0,116,255,  0,93,255,  0,70,255,  0,47,255,
+        0,24,255,  0,0,255,  19,0,255,  39,0,255,  58,0,255,
+        78,0,255,  98,0,255,  117,0,255,  137,0,255,  156,0,255,
+        176,0,255,  196,0,255,  215,0,255,  235,0,255,  255,0,255,
+        255,0,213,  255,0,170,  255,0,128,  255,0,85,  255,0,43,
+    };
+    return wheel[k * 3 + i];
+}
+PF_HD float pf_render_len(const PfRenderArgs& a, int y, int x, float u, float v) {
+    if (!(pf_finite(u) && pf_finite(v))) return pf_os_value(0x7fc00000u);
+    if (a.mode == 1) return sqrtf(u * u + v * v);
+    float ts, ps, te, pe;
+    pf_endpoint_sph((float)x, (float)y, 0.f, 0.f, a.H, a.W, ts, ps);
+    pf_endpoint_sph((float)x, (float)y, u, v, a.H, a.W, te, pe);
+    float hv = pf_haversine(pe - ps) + (cosf(ps) * cosf(pe)) * pf_haversine(te - ts);
+    hv = hv > 1.f ? 1.f : hv;               // an antipodal end point: sin^2 + cos^2 may round past 1, and asinf would give NaN for a finite flow
+    return 2.f * asinf(sqrtf(hv));
+}
+PF_HD PfRgb pf_render_pixel(float len, float u, float v, float clip) {
+    PfRgb o; o.c[0] = 0; o.c[1] = 0; o.c[2] = 0;
+    if (!(pf_finite(u) && pf_finite(v))) return o;
+    const float rad = (len < clip ? len : clip) / (clip + 1e-5f);
+    const float ang = atan2f(-v, -u) / 3.14159265358979323846f;
+    const float fk = (ang + 1.f) / 2.f * 54.f;
+    const float kf = floorf(fk);
+    int k0 = kf >= 0.f ? (kf <= 54.f ? (int)kf : 54) : 0;
+    const int k1 = k0 + 1 == 55 ? 0 : k0 + 1;
+    const float f = fk - kf;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 3; ++i) {
+        const float c0 = (float)pf_wheel(k0, i) / 255.f, c1 = (float)pf_wheel(k1, i) / 255.f;
+        float col = (1.f - f) * c0 + f * c1;
+        col = rad <= 1.f ? 1.f - rad * (1.f - col) : col * 0.75f;
+        const float q = floorf(255.f * col);
+        o.c[i] = (unsigned char)(q >= 0.f ? (q <= 255.f ? (int)q : 255) : 0);
+    }
+    return o;
+}
+PF_HD void pf_render_len_elem(long idx, const PfRenderArgs& a) {        // idx over B*H*W
+    const long N = (long)a.H * a.W, b = idx / N;
+    const int n = (int)(idx % N), y = n / a.W;
+    a.len[idx] = pf_render_len(a, y, n - y * a.W, a.flow[b * 2 * N + n], a.flow[(b * 2 + 1) * N + n]);
+}
+PF_HD void pf_render_put(const PfRenderArgs& a, long b, long n, const PfRgb& c) {
+    const long N = (long)a.H * a.W;
+    for (int i = 0; i < 3; ++i) {
+        const int ch = a.bgr ? 2 - i : i;
+        if (a.planar) a.out[(b * 3 + ch) * N + n] = c.c[i];
+        else a.out[(b * N + n) * 3 + ch] = c.c[i];
+    }
+}
+PF_HD void pf_render_color_elem(long idx, const PfRenderArgs& a) {      // idx over B*H*W
+    const long N = (long)a.H * a.W, b = idx / N, n = idx % N;
+    pf_render_put(a, b, n, pf_render_pixel(a.len[idx], a.flow[b * 2 * N + n], a.flow[(b * 2 + 1) * N + n], a.clip[b]));
+}
+
+// ----------------------------------------------------------------------------------------------
+// my_cycle_warp (core/utils/my_cycle_sample.py:100-115): out[b,c,y,x] = x sampled at (x + u, y + v) with cycle_grid_sample's taps
+// (x wraps, y clamps; is_grid = False), the taps of a pixel shared by its C channels; optionally the photometric residual
+// err[b,y,x] = mean over c of |ref - out| of the same launch.
+// ----------------------------------------------------------------------------------------------
+struct PfCycleWarpArgs { const float* x; const float* flo; const float* ref; float* out; float* err; int B, C, H, W; };
+PF_HD void pf_cycle_warp_elem(long idx, const PfCycleWarpArgs& a) {      // idx over B*H*W
+    const long N = (long)a.H * a.W, b = idx / N;
+    const int n = (int)(idx % N), y = n / a.W, x = n - y * a.W;
+    const PfWrapTaps t = pf_wraptaps((float)x + a.flo[b * 2 * N + n], (float)y + a.flo[(b * 2 + 1) * N + n], a.H, a.W);
+    float acc = 0.f;
+    for (int c = 0; c < a.C; ++c) {
+        const float* s = a.x + (b * a.C + c) * N;
+        const float w = pf_wrapmix(t, s[t.ia], s[t.ib], s[t.ic], s[t.id]);
+        a.out[(b * a.C + c) * N + n] = w;
+        if (a.err) acc = acc + fabsf(a.ref[(b * a.C + c) * N + n] - w);
+    }
+    if (a.err) a.err[idx] = acc / (float)a.C;
+}
+
+// Mean of x over the pixels with mask == 0 (mask NULL: all), per image: partials[(b*nblk + k)*2 + {0,1}] = fp64 sum and count of
+// pixel chunk k, then out[b] = sum / count in chunk order (0 when nothing is counted).  Deterministic: no atomics.
+#define PF_MM_BLOCKS 64
+struct PfMaskedMeanArgs { const float* x; const unsigned char* mask; double* partials; float* out; int B, N, nblk; };
+PF_HD void pf_masked_mean_final_elem(long b, const PfMaskedMeanArgs& a) {   // idx over B
+    double s = 0.0, c = 0.0;
+    for (int k = 0; k < a.nblk; ++k) { s += a.partials[(b * a.nblk + k) * 2]; c += a.partials[(b * a.nblk + k) * 2 + 1]; }
+    a.out[b] = c > 0.0 ? (float)(s / c) : 0.f;
+}

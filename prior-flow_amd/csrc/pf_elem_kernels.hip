@@ -1274,8 +1274,212 @@ int launch_fb_check(const PfFbCheckArgs& a, long total, void* stream) {
     return (int)hipGetLastError();
 }
 
+// ---- flow rendering -------------------------------------------------------------------------------------
+// The choice after pass p - 1 by one 256-thread workgroup: every thread sums a run of bins, a Hillis-Steele scan of the run sums,
+// and the one thread whose run holds the rank walks it.  sel = {new prefix, remaining rank}; pf_os_select_image is the statement.
+__device__ __forceinline__ void pf_os_block_select(const PfOrderStatArgs& a, int b, int p, unsigned* part, unsigned* sel) {
+    const unsigned* h = a.hist + (long)b * PF_OS_HIST + pf_os_hoff(p - 1);
+    const int nb = pf_os_nbins(p - 1), per = nb / 256, tid = threadIdx.x;
+    const int valid = p == 1 ? 2047 : nb;                                   // pass 0: the NaN bin is left out
+    const unsigned prefix = p == 1 ? 0u : a.state[b * 4 + (p - 2) * 2];
+    const unsigned rank = p == 1 ? pf_os_rank0(a.n, a.k, h[2047]) : a.state[b * 4 + (p - 2) * 2 + 1];
+    unsigned own = 0;
+    for (int j = tid * per; j < (tid + 1) * per; ++j) own += j < valid ? h[j] : 0u;
+    part[tid] = own;
+    if (tid == 0) { sel[0] = pf_os_prefix(prefix, 0u, p); sel[1] = 0u; }
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const unsigned t = tid >= d ? part[tid - d] : 0u;
+        __syncthreads();
+        part[tid] += t;
+        __syncthreads();
+    }
+    const unsigned incl = part[tid], excl = incl - own;
+    if (excl <= rank && rank < incl) {
+        unsigned cum = excl;
+        for (int j = tid * per; j < (tid + 1) * per; ++j) {
+            const unsigned c = j < valid ? h[j] : 0u;
+            if (cum + c > rank) { sel[0] = pf_os_prefix(prefix, (unsigned)j, p); sel[1] = rank - cum; break; }
+            cum += c;
+        }
+    }
+    __syncthreads();
+}
+
+// One pass of the select: grid (blocks, B).  Counts go to an LDS histogram; afterwards one integer atomic per non-empty bin and
+// workgroup.  SRC 0: the values are a.x; 1 / 2: pass 0 of pf_flow_render, the values are computed from the flow (one pixel / four
+// pixels of a row per thread) and stored to r.len on the way, so the flow is read once.
+template <int SRC>
+__global__ void __launch_bounds__(kBlock) pf_os_pass_kernel(const PfOrderStatArgs a, const PfRenderArgs r) {
+    __shared__ unsigned lh[2048];
+    __shared__ unsigned part[kBlock];
+    __shared__ unsigned sel[2];
+    const int b = blockIdx.y, tid = threadIdx.x, pass = a.pass;
+    for (int j = tid; j < 2048; j += kBlock) lh[j] = 0u;
+    unsigned prefix = 0u;
+    if (pass > 0) {
+        pf_os_block_select(a, b, pass, part, sel);
+        prefix = sel[0];
+        if (blockIdx.x == 0 && tid == 0) { a.state[b * 4 + (pass - 1) * 2] = sel[0]; a.state[b * 4 + (pass - 1) * 2 + 1] = sel[1]; }
+    } else {
+        __syncthreads();
+    }
+    const long stride = (long)gridDim.x * kBlock;
+    if (SRC == 0) {
+        const float* x = a.x + (long)b * a.n;
+        for (long i = (long)blockIdx.x * kBlock + tid; i < a.n; i += stride) {
+            const unsigned key = pf_os_key(x[i]);
+            if (pf_os_match(key, pass, prefix)) atomicAdd(&lh[pf_os_digit(key, pass)], 1u);
+        }
+    } else if (SRC == 1) {
+        const long N = a.n;
+        const float* f = r.flow + (long)b * 2 * N;
+        for (long i = (long)blockIdx.x * kBlock + tid; i < N; i += stride) {
+            const int y = (int)i / r.W;
+            const float v = pf_render_len(r, y, (int)i - y * r.W, f[i], f[N + i]);
+            r.len[(long)b * N + i] = v;
+            atomicAdd(&lh[pf_os_digit(pf_os_key(v), 0)], 1u);
+        }
+    } else {
+        const long N = a.n, N4 = N / 4;
+        const float* f = r.flow + (long)b * 2 * N;
+        for (long i = (long)blockIdx.x * kBlock + tid; i < N4; i += stride) {
+            const int n = (int)i * 4, y = n / r.W, x = n - y * r.W;
+            const float4 fu = *reinterpret_cast<const float4*>(f + n), fv = *reinterpret_cast<const float4*>(f + N + n);
+            float4 v;
+            v.x = pf_render_len(r, y, x, fu.x, fv.x);
+            v.y = pf_render_len(r, y, x + 1, fu.y, fv.y);
+            v.z = pf_render_len(r, y, x + 2, fu.z, fv.z);
+            v.w = pf_render_len(r, y, x + 3, fu.w, fv.w);
+            *reinterpret_cast<float4*>(r.len + (long)b * N + n) = v;
+            atomicAdd(&lh[pf_os_digit(pf_os_key(v.x), 0)], 1u);
+            atomicAdd(&lh[pf_os_digit(pf_os_key(v.y), 0)], 1u);
+            atomicAdd(&lh[pf_os_digit(pf_os_key(v.z), 0)], 1u);
+            atomicAdd(&lh[pf_os_digit(pf_os_key(v.w), 0)], 1u);
+        }
+    }
+    __syncthreads();
+    unsigned* gh = a.hist + (long)b * PF_OS_HIST + pf_os_hoff(pass);
+    const int nb = pf_os_nbins(pass);
+    for (int j = tid; j < nb; j += kBlock)
+        if (lh[j]) atomicAdd(gh + j, lh[j]);
+}
+// workgroups per image: `per` items per thread, at most 2048 workgroups.  A counting pass is memory-bound and pays one atomic per
+// non-empty bin and workgroup (8 items per thread); the length and colour kernels are bound by their arithmetic (sin / cos /
+// asin / atan2 per pixel) and want every CU busy at B = 1 (1 item per thread: 512 workgroups at 512x1024 instead of 64; their
+// times: profiles/r9_flow_viz_kernel_stats.csv).
+long pf_os_blocks(long items, int per) {
+    long blocks = (items + (long)kBlock * per - 1) / ((long)kBlock * per);
+    return blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+}
+int launch_os_pass(PfOrderStatArgs a, int pass, void* stream) {
+    a.pass = pass;
+    hipLaunchKernelGGL(pf_os_pass_kernel<0>, dim3((unsigned)pf_os_blocks(a.n, 8), (unsigned)a.B), dim3(kBlock), 0, (hipStream_t)stream,
+                       a, PfRenderArgs{});
+    return (int)hipGetLastError();
+}
+__global__ void __launch_bounds__(kBlock) pf_os_final_kernel(const PfOrderStatArgs a) {
+    __shared__ unsigned part[kBlock];
+    __shared__ unsigned sel[2];
+    pf_os_block_select(a, blockIdx.x, 3, part, sel);
+    if (threadIdx.x == 0) a.out[blockIdx.x] = pf_os_value(sel[0]);
+}
+int launch_os_final(const PfOrderStatArgs& a, void* stream) {
+    hipLaunchKernelGGL(pf_os_final_kernel, dim3((unsigned)a.B), dim3(kBlock), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+// four pixels of a row per thread: W % 4 == 0, flow and length maps 16-byte aligned, the image 4-byte aligned
+bool pf_render_vec(const PfRenderArgs& r) {
+    return r.W % 4 == 0 && ((uintptr_t)r.flow | (uintptr_t)r.len) % 16 == 0 && (uintptr_t)r.out % 4 == 0;
+}
+int launch_render_len(PfOrderStatArgs a, const PfRenderArgs& r, void* stream) {
+    a.pass = 0;
+    if (pf_render_vec(r))
+        hipLaunchKernelGGL(pf_os_pass_kernel<2>, dim3((unsigned)pf_os_blocks(a.n / 4, 1), (unsigned)a.B), dim3(kBlock), 0,
+                           (hipStream_t)stream, a, r);
+    else
+        hipLaunchKernelGGL(pf_os_pass_kernel<1>, dim3((unsigned)pf_os_blocks(a.n, 1), (unsigned)a.B), dim3(kBlock), 0,
+                           (hipStream_t)stream, a, r);
+    return (int)hipGetLastError();
+}
+// Colourise: every workgroup makes the last choice of the select itself (the clip of its image; workgroup 0 stores it), then
+// pf_render_pixel per pixel.  VEC: 16-byte loads of flow and length, twelve interleaved bytes as three dwords (planar: one dword
+// per plane); otherwise one pixel per thread through pf_render_put.
+template <bool VEC>
+__global__ void __launch_bounds__(kBlock) pf_render_color_kernel(const PfOrderStatArgs a, const PfRenderArgs r) {
+    __shared__ unsigned part[kBlock];
+    __shared__ unsigned sel[2];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    pf_os_block_select(a, b, 3, part, sel);
+    const float clip = pf_os_value(sel[0]);
+    if (blockIdx.x == 0 && tid == 0) a.out[b] = clip;
+    const long N = a.n, stride = (long)gridDim.x * kBlock;
+    const float* f = r.flow + (long)b * 2 * N;
+    const float* len = r.len + (long)b * N;
+    if (!VEC) {
+        for (long i = (long)blockIdx.x * kBlock + tid; i < N; i += stride) pf_render_put(r, b, i, pf_render_pixel(len[i], f[i], f[N + i], clip));
+        return;
+    }
+    for (long i = (long)blockIdx.x * kBlock + tid; i < N / 4; i += stride) {
+        const long n = i * 4;
+        const float4 fu = *reinterpret_cast<const float4*>(f + n), fv = *reinterpret_cast<const float4*>(f + N + n);
+        const float4 l = *reinterpret_cast<const float4*>(len + n);
+        PfRgb c[4] = {pf_render_pixel(l.x, fu.x, fv.x, clip), pf_render_pixel(l.y, fu.y, fv.y, clip),
+                      pf_render_pixel(l.z, fu.z, fv.z, clip), pf_render_pixel(l.w, fu.w, fv.w, clip)};
+        if (r.bgr) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { const unsigned char t = c[q].c[0]; c[q].c[0] = c[q].c[2]; c[q].c[2] = t; }
+        }
+        if (r.planar) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+                *reinterpret_cast<unsigned*>(r.out + ((long)b * 3 + ch) * N + n) =
+                    (unsigned)c[0].c[ch] | ((unsigned)c[1].c[ch] << 8) | ((unsigned)c[2].c[ch] << 16) | ((unsigned)c[3].c[ch] << 24);
+        } else {
+            unsigned* o = reinterpret_cast<unsigned*>(r.out + ((long)b * N + n) * 3);
+            o[0] = (unsigned)c[0].c[0] | ((unsigned)c[0].c[1] << 8) | ((unsigned)c[0].c[2] << 16) | ((unsigned)c[1].c[0] << 24);
+            o[1] = (unsigned)c[1].c[1] | ((unsigned)c[1].c[2] << 8) | ((unsigned)c[2].c[0] << 16) | ((unsigned)c[2].c[1] << 24);
+            o[2] = (unsigned)c[2].c[2] | ((unsigned)c[3].c[0] << 8) | ((unsigned)c[3].c[1] << 16) | ((unsigned)c[3].c[2] << 24);
+        }
+    }
+}
+int launch_render_color(const PfOrderStatArgs& a, const PfRenderArgs& r, void* stream) {
+    if (pf_render_vec(r))
+        hipLaunchKernelGGL(pf_render_color_kernel<true>, dim3((unsigned)pf_os_blocks(a.n / 4, 1), (unsigned)a.B), dim3(kBlock), 0,
+                           (hipStream_t)stream, a, r);
+    else
+        hipLaunchKernelGGL(pf_render_color_kernel<false>, dim3((unsigned)pf_os_blocks(a.n, 1), (unsigned)a.B), dim3(kBlock), 0,
+                           (hipStream_t)stream, a, r);
+    return (int)hipGetLastError();
+}
+// masked mean, stage 1: block (k, b) sums chunk k of image b in fp64 (wave shuffles, then LDS across the 4 waves)
+__global__ void __launch_bounds__(256) pf_masked_mean_kernel(const PfMaskedMeanArgs a) {
+    __shared__ double red[4][2];
+    const int k = blockIdx.x, b = blockIdx.y;
+    const int chunk = (a.N + a.nblk - 1) / a.nblk;
+    const int lo = k * chunk, hi = (lo + chunk < a.N) ? lo + chunk : a.N;
+    double s = 0.0, c = 0.0;
+    for (int n = lo + threadIdx.x; n < hi; n += 256)
+        if (!a.mask || a.mask[(long)b * a.N + n] == 0) { s += (double)a.x[(long)b * a.N + n]; c += 1.0; }
+    for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off); c += __shfl_down(c, off); }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = s; red[threadIdx.x >> 6][1] = c; }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        a.partials[((long)b * a.nblk + k) * 2 + threadIdx.x] =
+            ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+int launch_masked_mean(const PfMaskedMeanArgs& a, void* stream) {
+    hipLaunchKernelGGL(pf_masked_mean_kernel, dim3((unsigned)a.nblk, (unsigned)a.B), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
+#define PF_OS_PASS_LAUNCH(a, pass, stream) launch_os_pass(a, pass, stream)
+#define PF_OS_FINAL_LAUNCH(a, stream) launch_os_final(a, stream)
+#define PF_RENDER_LEN_LAUNCH(o, r, stream) launch_render_len(o, r, stream)
+#define PF_RENDER_COLOR_LAUNCH(o, r, stream) launch_render_color(o, r, stream)
+#define PF_MASKED_MEAN_LAUNCH(a, stream) launch_masked_mean(a, stream)
 #define PF_FB_CHECK_LAUNCH(a, total, stream) launch_fb_check(a, total, stream)
 #define PF_LOOKUP_BWD_LAUNCH(a, total, stream) launch_lookup_bwd(a, total, stream)
 #define PF_UPSAMPLE_BWD_LAUNCH(a, total, stream) launch_upsample_bwd(a, total, stream)
