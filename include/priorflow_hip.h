@@ -660,6 +660,13 @@ int pf_dccl_lookup_bwd(const float* coords, const float* g_w2c, const float* d_o
  * x: channel-last, two-segment virtual concat like pf_conv_desc (in0 | in1); dy: channel-last gradient of the
  * conv's pre-activation output; dw: fp32 in the packed weight layout [Cout_pad128][KH*KW][Cin_pad32], db
  * [Cout_pad128] or NULL -- both ACCUMULATED into (zero them first).  3x3, 1x5, 5x1, 1x1; 3-pass bf16 split.
+ * Rows >= cout and columns >= c0 + c1 of dw, and db[cout ...], are never written.
+ * Split-K promise: the 4 x 32 pixel tiles (per image) are dealt round-robin to
+ *   nsplit = min(ceil(512 / (ceil(cout / 128) * ceil(cin_pad / (kh * kw > 5 ? 32 : 64)))), tiles)
+ * splits -- at most 512 --, split s owning tiles s, s + nsplit, ...; each split adds its fp32 partial sums with one atomic per
+ * element, in arbitrary order (results are not bit-reproducible).
+ * PF_ERR_BAD_ARG: a NULL x0 / dy / dw (or x1 with c1 > 0), a slice off + c past its row ld.  PF_ERR_BAD_SHAPE: another kernel
+ * shape; cout, c0, c1, an ld or an offset that is not a multiple of 4; c1 > 0 with c0 % 32 != 0; B, H8, W8, c0, cout < 1.
  * The data gradient needs no entry of its own: dx = pf_conv2d(dy, W') with
  * W'[c][o][ky][kx] = W[o][c][KH-1-ky][KW-1-kx]. */
 int pf_conv2d_wgrad(const float* x0, int ld0, int off0, int c0, const float* x1, int ld1, int off1, int c1,
@@ -670,7 +677,9 @@ int pf_conv2d_wgrad(const float* x0, int ld0, int off0, int c0, const float* x1,
  * core/update.py:87,173,175 2->128 stride 1; their inputs carry no gradient): exact fp32,
  *   dw[o][c][ky][kx] += sum_p dy[p][o] * x[stride*p + (ky,kx) - pad][c],  db[o] += sum_p dy[p][o]
  * x: NCHW planes (nchw != 0) or a channel-last slice; dy: channel-last [B*Hout*Wout][ld_dy]; dw in the framework's own
- * parameter layout [Cout][Cin][KH][KW]; dw, db ACCUMULATED.  cin <= 4, kh*kw <= 52, stride 1 | 2. */
+ * parameter layout [Cout][Cin][KH][KW]; dw, db ACCUMULATED.  cin <= 4, kh*kw <= 52, stride 1 | 2 (PF_ERR_BAD_SHAPE otherwise,
+ * as for cout, ld_dy or off_dy that is not a multiple of 4); PF_ERR_BAD_ARG: a NULL x / dy / dw, a slice past its row, and for
+ * the _ws form a NULL workspace or one shorter than pf_conv2d_wgrad_small_ws_floats(...). */
 int pf_conv2d_wgrad_small(const float* x, int nchw, int ld_in, int off_in, int cin,
                           const float* dy, int ld_dy, int off_dy, int cout, float* dw, float* db,
                           int kh, int kw, int stride, int B, int Hout, int Wout, void* stream);

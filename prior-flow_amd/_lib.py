@@ -625,9 +625,17 @@ class PfLib:
         stream = self._stream(like) if like is not None else C.c_void_p(torch.cuda.current_stream().cuda_stream)
         self._rc(self._dll.pf_debug_dirty_lds(C.c_uint(pattern & 0xffffffff), stream), "pf_debug_dirty_lds")
 
-    def conv2d_wgrad_small(self, x, nchw, off_in, cin, dy, off_dy, cout, dw, db, kh, kw, stride, B, Hout, Wout):
-        """dw [Cout,Cin,KH,KW] (+= ), db [Cout] (+= or None) of a small-Cin convolution; x NCHW planes or channel-last."""
+    def conv2d_wgrad_small(self, x, nchw, off_in, cin, dy, off_dy, cout, dw, db, kh, kw, stride, B, Hout, Wout, one_stage=False):
+        """dw [Cout,Cin,KH,KW] (+= ), db [Cout] (+= or None) of a small-Cin convolution; x NCHW planes or channel-last.
+        one_stage: the pf_conv2d_wgrad_small entry (one atomic per weight per workgroup, no workspace) instead of the
+        two-stage pf_conv2d_wgrad_small_ws the product uses."""
         self._chk(x, dy, dw, db)
+        if one_stage:
+            self._rc(self._dll.pf_conv2d_wgrad_small(_ptr(x), int(nchw), 0 if nchw else x.shape[-1], off_in, cin,
+                                                     _ptr(dy), dy.shape[-1], off_dy, cout, _ptr(dw), _ptr(db),
+                                                     kh, kw, stride, B, Hout, Wout, self._stream(x)),
+                     "pf_conv2d_wgrad_small")
+            return
         n = int(self._dll.pf_conv2d_wgrad_small_ws_floats(cin, cout, kh, kw, B, Hout, Wout))
         ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)      # per call: two streams may run stems side by side
         self._rc(self._dll.pf_conv2d_wgrad_small_ws(_ptr(x), int(nchw), 0 if nchw else x.shape[-1], off_in, cin,

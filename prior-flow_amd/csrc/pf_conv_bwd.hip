@@ -1,7 +1,16 @@
-// Convolution backward building blocks (the tape that would use them is not built yet).
+// Convolution backward: the weight and bias gradients of a training step.  Callers: the autograd Functions of
+// autograd.py (one launch per convolution use, or one per convolution through a WeightGrad accumulator) and the refinement
+// loop's hand-written backward (train_loop.py: one deferred launch per convolution over the iters * B stored images).
 //
-//   pf_conv2d_wgrad:  dW[o][tap][c] += sum_p dY[p][o] * X[p + off(tap)][c]      (stride 1, zero padding)
-//   pf_col_sums:      db[o]          = sum_p dY[p][o]
+//   pf_conv2d_wgrad:        dW[o][tap][c] += sum_p dY[p][o] * X[p + off(tap)][c]      (stride 1, zero padding)
+//                           db[o]         += sum_p dY[p][o]                           (fused: the same launch, when db is given)
+//   pf_conv2d_wgrad_small:  the 7x7 stems (Cin <= 4, stride 1 | 2), further down; _ws is its two-stage form
+//
+// Contract of pf_conv2d_wgrad's split-K (tests/test_hip_conv_bwd.py and tests/wgrad_launches.py rely on it): the pixel tiles
+// (4 x 32, per image) are dealt round-robin to nsplit = min(ceil(512 / workgroups per split), tiles) splits, with
+// workgroups per split = ceil(Cout / 128) * ceil(Cin_pad / (64, or 32 for more than 5 taps)); so there are AT MOST 512 SPLITS,
+// split s owns tiles s, s + nsplit, ..., and a launch with more than 512 tiles runs the pipelined loop more than once per
+// split.  Each split adds its partial sums to dW (and db) with one fp32 atomic per element.
 //
 // (dgrad needs no kernel of its own: dX = conv(dY, W') with W'[c][o][ky][kx] = W[o][c][KH-1-ky][KW-1-kx]
 //  runs on pf_conv2d -- engine.Conv.dgrad_of.)

@@ -1,11 +1,13 @@
 """Convolution backward building blocks (SURVEY.md 8f-3 groundwork) against torch autograd on the CPU:
 pf_conv2d_wgrad (weight + bias gradient, transposed-LDS-read MFMA kernel) and the data gradient through
-pf_conv2d on flipped / transposed weights (engine.Conv.dgrad_of)."""
+pf_conv2d on flipped / transposed weights (engine.Conv.dgrad_of).  Further down, directed cases of both weight-gradient kernels
+against float64 under the derived bounds of tests/wgrad_launches.py: splits / workgroups that own several pixel tiles."""
 import pytest
 import torch
 
 import golden_cases as gc
 import kernel_cases as kc
+import wgrad_launches as wl
 
 pytestmark = pytest.mark.gpu
 
@@ -96,6 +98,81 @@ def test_small_cin_wgrad_vs_autograd(lib, case):
     xcl[:, 2:2 + cin] = kc.cl(x).to(dev)
     lib.conv2d_wgrad_small(xcl, False, 2, cin, dy, 4, cout, dw, None, k, k, stride, B, Ho, Wo)      # accumulates
     kc.check(dw, 2 * w.grad, 2 * tol, "weight gradient accumulates (channel-last input)")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Directed cases against float64 under the derived bounds of tests/wgrad_launches.py (independent of what the product launches)
+# ---------------------------------------------------------------------------------------------------------------------
+def _replay(lib, launch, seed, **kwargs):
+    """One case: a launch, both bounds, the padding pattern and the sentinels; a second launch (without db when it has one:
+    db then stays at 1x) must give 2x.  Prints the worst err / bound ratios."""
+    dev = torch.device("cuda")
+    case = wl.build_case(launch, launch.B, launch.H, launch.W, dev, seed=seed)
+    ref = wl.reference(case)
+    wl.run_case(lib, case, **kwargs)
+    fails, worst = wl.check_case(case, ref, 1.0)
+    db = case.T.pop("db", None)                       # second launch: dw accumulates, db is not passed
+    wl.run_case(lib, case, **kwargs)
+    if db is not None:
+        case.T["db"] = db
+    fails2, worst2 = wl.check_case(case, ref, 2.0, db_mult=1.0)
+    print(f"\n{wl.sig_str(launch)}: worst err / bound dw {worst['dw'][0]:.3g} / {worst['dw'][1]:.3g} (2x: {worst2['dw'][0]:.3g} / "
+          f"{worst2['dw'][1]:.3g}), db {worst['db'][0]:.3g} / {worst['db'][1]:.3g}")
+    assert not fails and not fails2, "\n".join(fails + ["after the second launch:"] + fails2)
+
+
+# B = 1103 (a prime) images of 3x29: every image is ONE partial tile, so consecutive tiles of a split lie in different images, and
+# with the at most 512 splits pf_conv2d_wgrad's header promises every split owns two or more tiles and no split count divides 1103.
+# 3 x 150x300: 380 tiles per image, partial on both edges, 1140 in all.
+WG_GEOMETRIES = [(1103, 3, 29), (3, 150, 300)]
+# (c0, c1, off1, cout, off_dy, pad_dy, db): single segment; [32 | 64] two segments; cout 4 and 124 at a non-zero off_dy
+WG_CHANNELS = [(64, 0, 0, 64, 0, 0, True), (32, 64, 8, 124, 8, 12, False), (32, 0, 0, 4, 128, 4, True), (32, 64, 0, 124, 4, 0, True)]
+
+
+@pytest.mark.parametrize("geo", WG_GEOMETRIES, ids=lambda g: "x".join(map(str, g)))
+@pytest.mark.parametrize("ch", WG_CHANNELS, ids=lambda c: "c%d+%d-o%d@%d%s" % (c[0], c[1], c[3], c[4], "-db" if c[6] else ""))
+@pytest.mark.parametrize("k", [(3, 3), (1, 5), (5, 1), (1, 1)], ids=lambda k: "%dx%d" % k)
+def test_wgrad_splits_that_own_several_tiles(lib, k, ch, geo):
+    c0, c1, off1, cout, off_dy, pad_dy, db = ch
+    B, H, W = geo
+    ln = wl.mfma_launch(k[0], k[1], c0, cout, B, H, W, c1=c1, off1=off1, pad0=4, pad1=8, off_dy=off_dy, pad_dy=pad_dy, db=db)
+    nt, ns = wl.tiles(ln), wl.mfma_splits(ln)
+    assert ns <= 512 and nt >= 2 * ns and nt % ns, (nt, ns)          # every split owns two or more tiles, unevenly
+    _replay(lib, ln, seed=hash((k, ch, geo)) % 10007)
+
+
+def _small_groups(lib, ln):
+    """Workgroups per 64-channel column block of a pf_conv2d_wgrad_small launch, from the workspace the library asks for."""
+    a = ln.args
+    n = int(lib._dll.pf_conv2d_wgrad_small_ws_floats(a["cin"], a["cout"], a["kh"], a["kw"], ln.B, ln.H, ln.W))
+    per = ((a["cout"] + 63) // 64) * (a["kh"] * a["kw"] * a["cin"] + 1) * 64
+    assert n > 0 and n % per == 0
+    return n // per
+
+
+# (cin, cout, kh, kw, stride, nchw, off_in): 521 images of 7x5 outputs (one partial 8x8 tile each)
+WS_CASES = [(1, 96, 7, 7, 1, False, 3), (2, 100, 7, 7, 1, False, 2), (3, 96, 7, 7, 2, True, 0), (4, 100, 7, 7, 2, False, 0),
+            (1, 100, 3, 3, 2, True, 0), (2, 96, 7, 7, 2, False, 0), (3, 100, 5, 5, 1, False, 1), (4, 96, 3, 7, 1, True, 0)]
+
+
+@pytest.mark.parametrize("one_stage", [False, True], ids=["ws", "one-stage"])
+@pytest.mark.parametrize("case", WS_CASES, ids=lambda c: "cin%d-o%d-%dx%d-s%d-%s" % (c[0], c[1], c[2], c[3], c[4], "nchw" if c[5] else "cl%d" % c[6]))
+def test_small_cin_wgrad_workgroups_that_walk_several_tiles(lib, case, one_stage):
+    """Both entries on the same inputs: the two-stage pf_conv2d_wgrad_small_ws the product calls and the one-stage
+    pf_conv2d_wgrad_small."""
+    cin, cout, kh, kw, stride, nchw, off_in = case
+    ln = wl.small_launch(cin, cout, kh, kw, stride, 521, 7, 5, nchw=nchw, off_in=off_in, pad_in=1, off_dy=4, pad_dy=8)
+    groups, nt = _small_groups(lib, ln), wl.tiles(ln)
+    assert nt > 2 * groups and nt % groups, (nt, groups)           # more than two tiles per workgroup, unevenly
+    _replay(lib, ln, seed=hash(case) % 10007, one_stage=one_stage)
+
+
+@pytest.mark.parametrize("one_stage", [False, True], ids=["ws", "one-stage"])
+def test_small_cin_wgrad_with_an_empty_reduce_slice(lib, one_stage):
+    """9 workgroups: the second stage's 8 slices take 2 workgroups each, so slices 5..7 are empty."""
+    ln = wl.small_launch(2, 100, 7, 7, 1, 9, 7, 5, nchw=False, off_in=2, pad_in=0, off_dy=0, pad_dy=4)
+    assert _small_groups(lib, ln) == 9
+    _replay(lib, ln, seed=99, one_stage=one_stage)
 
 
 def test_training_ops_without_pytorch_kernels(lib):
