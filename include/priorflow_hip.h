@@ -136,6 +136,37 @@ int pf_flow_render(const float* flow, unsigned char* out, void* scratch, long sc
 int pf_cycle_warp(const float* x, const float* flo, const float* ref, float* out, float* err, int B, int C, int H, int W,
                   void* stream);
 
+/* Training augmentation for the 360-degree sets: what FlowDataset_360.__getitem__ with
+ * FlowAugmentor_360(do_flip=False) delivers (core/datasets.py:137-159, core/utils/augmentor.py:210-316), for B samples at once.
+ *   img1, img2: [B,H,W,3] bytes as decoded; flow: [B,H,W,2] fp32 as decoded; params: [B][PF_AUG_ROW] 32-bit words, one row
+ *   per sample (the layout: csrc/pf_augment.h, mirrored by prior_flow_amd.augment.AugmentParams), already on the device.
+ *   image1, image2: [B,3,H,W] fp32 (integer values 0..255); flow_gt: [B,2,H,W]; valid: [B,H,W] (0 / 1), fp32.
+ * Per sample, in the reference's order: u = (u + W/2) % W - W/2 (datasets.py:138); the colour step (augmentor.py:228-239: one
+ * ColorJitter draw on the stack of both images, or one per image when the row's asymmetric bit is set; torchvision's PIL
+ * backend: 8 bits after every operation, Image.blend in fp32 with truncation, Pillow's L and HSV; the contrast mean
+ * int(mean(L) + 0.5) is taken over what the draw is applied to); the eraser (:241-252: up to two rectangles clipped at the border,
+ * filled in image 2 with its truncated per-channel mean after the colour step); the yaw roll (:254-283: out[:, (m + r) % W] =
+ * in[:, m]; image 1 and the flow by r1, image 2 by r2, and u = u_clip((u + r2) - r1) when the row's asymmetric-roll bit is
+ * set); valid = |u| < 1000 & |v| < 1000 (datasets.py:158; NaN gives 0).
+ * Four launches on `stream`, no host read, no allocation, capturable: zero the sums; the L sums for the contrast means; the
+ * main pass (chain, roll, flow, valid, image 2's channel sums); the eraser.  All sums are 64-bit integers (one atomic per
+ * workgroup and quantity), so repeated launches are identical.  Four output pixels of a row per thread when W % 4 == 0 and the
+ * four outputs are 16-byte aligned, one pixel per thread otherwise: the same per-pixel functions, the same bytes.
+ * A row's values are not trusted: rolls are reduced mod W, rectangles clipped, unknown operations skipped.
+ * scratch: at least pf_augment_scratch_bytes(B) bytes, 8-byte aligned, overwritten.
+ * PF_ERR_BAD_ARG: a NULL pointer, two outputs that are the same, a misaligned scratch / params / flow, scratch_bytes too small.
+ * PF_ERR_BAD_SHAPE: B < 1, B > PF_MAX_IMAGES, H or W < 2, H * W >= 2^30. */
+#define PF_AUG_ROW_WORDS 32
+long pf_augment_scratch_bytes(int B);
+int pf_augment_360(const unsigned char* img1, const unsigned char* img2, const float* flow, const int* params, float* image1,
+                   float* image2, float* flow_gt, float* valid, void* scratch, long scratch_bytes, int B, int H, int W,
+                   void* stream);
+/* Pillow's 8-bit Image.convert between RGB and HSV on n interleaved pixels: mode 0 RGB -> HSV, 1 HSV -> RGB.  The two halves of
+ * the hue step of pf_augment_360, callable on their own: a parameter row can only run the round trip, and HSV -> RGB alone is
+ * held to Pillow bit for bit on the device as well.  PF_ERR_BAD_ARG: NULL, in == out, another mode; PF_ERR_BAD_SHAPE: n < 1 or
+ * n >= 2^30. */
+int pf_augment_convert(const unsigned char* in, unsigned char* out, long n, int mode, void* stream);
+
 /* out[b] = mean of x[b, :] over the elements with mask[b, n] == 0 (mask NULL: all of them; nothing counted: 0).  x: [B,N] fp32,
  * mask: [B,N] bytes.  fp64 sums of at most 64 chunks per image, then one sum in chunk order: deterministic, two launches, no
  * host read.  scratch: at least 1024 * B bytes, 8-byte aligned.  PF_ERR_BAD_ARG: a NULL x / out / scratch, out == x, scratch

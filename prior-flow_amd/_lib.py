@@ -160,8 +160,15 @@ _SIGNATURES = {
     "pf_flow_render": [_fp, _fp, _fp, C.c_long, _i, _i, _i, _i, C.c_double, _i, _i, _fp],
     "pf_cycle_warp": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp],
     "pf_masked_mean": [_fp, _fp, _fp, _fp, C.c_long, _i, _i, _fp],
+    "pf_augment_scratch_bytes": [_i],
+    "pf_augment_360": [_fp] * 9 + [C.c_long, _i, _i, _i, _fp],
+    "pf_augment_convert": [_fp, _fp, C.c_long, _i, _fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
+# entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp): a host-only handle
+# (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+_OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert")
+AUG_ROW_WORDS = 32                                  # PF_AUG_ROW_WORDS
 
 
 class PfError(RuntimeError):
@@ -238,7 +245,7 @@ class PfLib:
             try:
                 fn = getattr(self._dll, name)
             except AttributeError:
-                if name in optional:
+                if name in optional or (not require_cuda and name in _OWN_EMULATION):
                     self.missing.append(name)
                     continue
                 raise PfError(f"{path} does not export {name}")
@@ -996,6 +1003,50 @@ class PfLib:
             raise PfError("cycle_warp: ref [B,C,H,W] and err [B,H,W] go together")
         self._rc(self._dll.pf_cycle_warp(_ptr(x), _ptr(flo), _ptr(ref), _ptr(out), _ptr(err), B, Cc, H, W, self._stream(x)),
                  "pf_cycle_warp")
+        return out
+
+    # ---- training augmentation -----------------------------------------
+    def _have(self, name: str):
+        if name in self.missing:
+            raise PfError(f"{self.path} does not export {name}")
+
+    def augment_scratch_bytes(self, B: int) -> int:
+        self._have("pf_augment_scratch_bytes")
+        r = self._dll.pf_augment_scratch_bytes(B)
+        self._rc(min(r, 0), "pf_augment_scratch_bytes")
+        return r
+
+    def augment_360(self, img1, img2, flow, params, image1, image2, flow_gt, valid, scratch):
+        """FlowAugmentor_360 and the loader steps around it on B samples (pf_augment_360): img1, img2 uint8 [B,H,W,3], flow fp32
+        [B,H,W,2], params int32 [B, AUG_ROW_WORDS] -> image1, image2 [B,3,H,W], flow_gt [B,2,H,W], valid [B,H,W], fp32."""
+        self._have("pf_augment_360")
+        if img1.dim() != 4 or img1.shape[3] != 3:
+            raise PfError(f"augment_360: img1 {tuple(img1.shape)}, expected [B,H,W,3]")
+        B, H, W, _ = img1.shape
+        self._chk_bytes(img1, "augment_360: img1", torch.uint8)
+        self._chk_bytes(img2, "augment_360: img2", torch.uint8)
+        self._chk_bytes(params, "augment_360: params", torch.int32)
+        self._chk_bytes(scratch, "augment_360: scratch")
+        self._chk(flow, image1, image2, flow_gt, valid)
+        want = ((img2, (B, H, W, 3)), (flow, (B, H, W, 2)), (params, (B, AUG_ROW_WORDS)), (image1, (B, 3, H, W)),
+                (image2, (B, 3, H, W)), (flow_gt, (B, 2, H, W)), (valid, (B, H, W)))
+        for t, shape in want:
+            if tuple(t.shape) != shape:
+                raise PfError(f"augment_360: a tensor of shape {tuple(t.shape)} where {shape} is expected (img1 {tuple(img1.shape)})")
+        self._rc(self._dll.pf_augment_360(_ptr(img1), _ptr(img2), _ptr(flow), _ptr(params), _ptr(image1), _ptr(image2),
+                                          _ptr(flow_gt), _ptr(valid), _ptr(scratch), scratch.numel() * scratch.element_size(),
+                                          B, H, W, self._stream(img1)), "pf_augment_360")
+        return image1, image2, flow_gt, valid
+
+    def augment_convert(self, src, out, to_rgb: bool):
+        """Pillow's 8-bit RGB -> HSV (to_rgb False) or HSV -> RGB on interleaved pixels [..., 3] (pf_augment_convert)."""
+        self._have("pf_augment_convert")
+        self._chk_bytes(src, "augment_convert: src", torch.uint8)
+        self._chk_bytes(out, "augment_convert: out", torch.uint8)
+        if src.dim() < 1 or src.shape[-1] != 3 or out.shape != src.shape:
+            raise PfError(f"augment_convert: src {tuple(src.shape)} / out {tuple(out.shape)}, expected equal shapes [..., 3]")
+        self._rc(self._dll.pf_augment_convert(_ptr(src), _ptr(out), src.numel() // 3, int(bool(to_rgb)), self._stream(src)),
+                 "pf_augment_convert")
         return out
 
     def masked_mean(self, x, mask, out, scratch):
