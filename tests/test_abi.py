@@ -63,6 +63,19 @@ def test_null_and_shape_errors_are_reported_without_a_gpu(built_lib):
     assert dll.pf_conv2d(None, 1, 1, 16, 32, None) == -1
     assert dll.pf_corr_pyramid(None, None, None, None, None, None, 1, 16, 32, 256, None) == -1
     assert dll.pf_prepare_images(None, None, None, None, None, 1, 128, 256, None) == -1
+    # the two training kernels without a unit case of their own before tests/elem_launches.py: null pointers, then (with live host
+    # pointers, nothing is launched) the shape checks -- a row shorter than C + wout, no rows, aliased moments, no elements
+    L, Fl = ctypes.c_long, ctypes.c_float
+    buf = [(ctypes.c_float * 8)() for _ in range(5)]
+    assert dll.pf_gru_dx_finish(None, 8, None, 8, None, 8, None, 8, None, 8, L(1), 4, 4, None) == -1
+    assert dll.pf_gru_dx_finish(buf[0], 7, buf[1], 8, buf[2], 8, buf[3], 4, buf[4], 4, L(1), 4, 4, None) == -2
+    assert dll.pf_gru_dx_finish(buf[0], 8, buf[1], 8, buf[2], 8, buf[3], 3, buf[4], 4, L(1), 4, 4, None) == -2
+    assert dll.pf_gru_dx_finish(buf[0], 8, buf[1], 8, buf[2], 8, buf[3], 4, buf[4], 4, L(0), 4, 4, None) == -2
+    assert dll.pf_adamw_step_dev(None, None, None, None, L(8), Fl(0.9), Fl(0.999), Fl(1e-8), None, None) == -1
+    assert dll.pf_adamw_step_dev(buf[0], buf[1], buf[2], buf[2], L(8), Fl(0.9), Fl(0.999), Fl(1e-8), buf[4], None) == -1
+    assert dll.pf_adamw_step_dev(buf[0], buf[1], buf[2], buf[3], L(8), Fl(0.9), Fl(0.999), Fl(1e-8), None, None) == -1
+    assert dll.pf_adamw_step_dev(buf[0], buf[1], buf[2], buf[3], L(0), Fl(0.9), Fl(0.999), Fl(1e-8), buf[4], None) == -2
+    assert dll.pf_adamw_step_dev(buf[0], buf[1], buf[2], buf[3], L(8), Fl(1.0), Fl(0.999), Fl(1e-8), buf[4], None) == -2
 
 
 def test_conv_launch_plan_is_host_logic(built_lib, monkeypatch):

@@ -21,17 +21,8 @@ NEW = ("pf_forward_interpolate", "pf_prepare_frame")
 
 @pytest.fixture(scope="module")
 def emu():
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not available")
-    srcs = [os.path.join(EMU_DIR, "pf_emu.cpp"), os.path.join(CSRC, "pf_elem.h"),
-            os.path.join(CSRC, "pf_api_elem.inc"), os.path.join(CSRC, "pf_common.h")]
-    if not os.path.exists(EMU_SO) or any(os.path.getmtime(s) > os.path.getmtime(EMU_SO) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off",
-                               "-I", CSRC, srcs[0], "-o", EMU_SO])
-    from prior_flow_amd._lib import PfLib
-    return PfLib(EMU_SO, require_cuda=False, optional=("pf_debug_dirty_lds", "pf_conv2d", "pf_conv2d_tile", "pf_conv2d_stats_blocks", "pf_conv2d_roles", "pf_corr_pyramid", "pf_corr_pyramid_bf16x3", "pf_conv2d_wgrad",
-                                                            "pf_dccl_combine_conv1x1", "pf_conv2d_wgrad_small", "pf_conv2d_wgrad_small_ws",
-                                                            "pf_conv2d_wgrad_small_ws_floats", "pf_enc_stem"))
+    import emu_lib
+    return emu_lib.load()
 
 
 def flows(kind: str, h: int, w: int, seed: int = 0) -> np.ndarray:

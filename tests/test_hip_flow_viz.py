@@ -37,12 +37,8 @@ def gold():
 
 @pytest.fixture(scope="module")
 def emu():
-    from prior_flow_amd._lib import PfLib
-    import __graft_entry__ as ge
-    return PfLib(ge.build_emu(), require_cuda=False, optional=(
-        "pf_debug_dirty_lds", "pf_conv2d", "pf_conv2d_tile", "pf_conv2d_stats_blocks", "pf_conv2d_roles", "pf_corr_pyramid",
-        "pf_corr_pyramid_bf16x3", "pf_conv2d_wgrad", "pf_dccl_combine_conv1x1", "pf_conv2d_wgrad_small", "pf_conv2d_wgrad_small_ws",
-        "pf_conv2d_wgrad_small_ws_floats", "pf_enc_stem"))
+    import emu_lib
+    return emu_lib.load()
 
 
 # ---- the order statistic ---------------------------------------------------------------------------------------------------
