@@ -2,7 +2,9 @@
 // Compiles prior-flow_amd/csrc/pf_elem.h + pf_api_elem.inc for the CPU so that the sampler /
 // geometry / lookup index logic can be checked against the oracle in the GPU-less build
 // container (tests/test_emu_kernels.py).  The product never loads this library; the MFMA
-// kernels (pf_conv2d, pf_corr_pyramid) have no emulation and are tested on the GPU only.
+// kernels (pf_conv2d, pf_corr_pyramid, pf_enc_stem) have no emulation here: on the GPU every launch of theirs is held to a
+// float64 reference under derived bounds (tests/conv_launches.py, tests/mfma_launches.py), and on the CPU torch emulations of
+// their arithmetic go through the same references and bounds (tests/test_mfma_launch_reference.py).
 #include "pf_elem.h"
 
 template <class Args, void (*F)(long, const Args&)>

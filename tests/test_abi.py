@@ -73,6 +73,28 @@ def test_null_and_shape_errors_are_reported_without_a_gpu(built_lib):
     assert dll.pf_gru_dx_finish(buf[0], 8, buf[1], 8, buf[2], 8, buf[3], 4, buf[4], 4, L(0), 4, 4, None) == -2
     assert dll.pf_adamw_step_dev(None, None, None, None, L(8), Fl(0.9), Fl(0.999), Fl(1e-8), None, None) == -1
     assert dll.pf_adamw_step_dev(buf[0], buf[1], buf[2], buf[2], L(8), Fl(0.9), Fl(0.999), Fl(1e-8), buf[4], None) == -1
+    # the corr build on pre-split operands, the encoders' stem and the f16 split (tests/mfma_launches.py runs them): null
+    # pointers, then the shape checks with live host pointers -- all of them answer before anything is launched
+    p = [(ctypes.c_float * 8)() for _ in range(6)]
+    assert dll.pf_corr_pyramid_bf16x3(None, None, None, None, None, None, 1, 16, 32, 256, None) == -1
+    assert dll.pf_corr_pyramid_bf16x3(p[0], p[1], p[2], p[3], p[4], None, 1, 16, 32, 256, None) == -1
+    assert dll.pf_corr_pyramid_bf16x3(*p, 1, 16, 32, 48, None) == -2               # C % 32 != 0
+    assert dll.pf_corr_pyramid_bf16x3(*p, 1, 15, 32, 256, None) == -2              # level 3 smaller than 2 x 2
+    assert dll.pf_corr_pyramid_bf16x3(*p, 1, 16, 15, 256, None) == -2
+    assert dll.pf_corr_pyramid_bf16x3(*p, 1, 2048, 4096, 256, None) == -2          # H8 * W8 * C = 2^31: 32-bit row offsets
+    assert dll.pf_corr_pyramid(*p, 1, 2048, 4096, 256, None) == -2
+    assert dll.pf_enc_stem(None, None, None, None, None, 0, None, 1, 16, 64, None) == -1
+    assert dll.pf_enc_stem(p[0], p[1], p[2], None, None, 0, None, 1, 16, 64, None) == -1       # neither rows nor twin
+    assert dll.pf_enc_stem(p[0], p[1], p[2], p[3], None, 0, None, 1, 17, 64, None) == -2       # odd H
+    assert dll.pf_enc_stem(p[0], p[1], p[2], p[3], None, 0, None, 1, 16, 63, None) == -2
+    assert dll.pf_enc_stem(p[0], p[1], p[2], p[3], None, 0, None, 1, 14, 64, None) == -2       # H < 16
+    assert dll.pf_enc_stem(p[0], p[1], p[2], p[3], None, 0, None, 0, 16, 64, None) == -2
+    assert dll.pf_split_f16(None, 8, None, 1, L(1), 8, None) == -1
+    assert dll.pf_split_f16(p[0], 8, p[0], 1, L(1), 8, None) == -1                 # in place
+    assert dll.pf_split_f16(p[0], 8, p[1], 1, L(1), 6, None) == -2                 # C % 4 != 0
+    assert dll.pf_split_f16(p[0], 4, p[1], 1, L(1), 8, None) == -2                 # ld_in < C
+    assert dll.pf_split_f16(p[0], 128, p[1], 1, L(1), 128, None) == -2             # the map's row is shorter than C
+    assert dll.pf_split_f16(p[0], 8, p[1], 1, L(0), 8, None) == -2                 # no rows
     assert dll.pf_adamw_step_dev(buf[0], buf[1], buf[2], buf[3], L(8), Fl(0.9), Fl(0.999), Fl(1e-8), None, None) == -1
     assert dll.pf_adamw_step_dev(buf[0], buf[1], buf[2], buf[3], L(0), Fl(0.9), Fl(0.999), Fl(1e-8), buf[4], None) == -2
     assert dll.pf_adamw_step_dev(buf[0], buf[1], buf[2], buf[3], L(8), Fl(1.0), Fl(0.999), Fl(1e-8), buf[4], None) == -2
