@@ -235,7 +235,9 @@ int pf_unpack_wgrads(const pf_unpack_job* jobs, int n, void* stream);
 int pf_pack_conv_weights(const float* w0, int cout0, const float* w1, int cout1, const float* b0, const float* b1,
                          int cin, int kh, int kw, int mode, int cin_rot, void* dst_w, float* dst_b,
                          int cout_pad, int cin_pad, void* stream);
-/* Several of them per launch (16 jobs each; the arguments of pf_pack_conv_weights as a struct). */
+/* Several of them per launch (16 jobs each; the arguments of pf_pack_conv_weights as a struct).  The jobs of one launch are
+ * validated just before that launch: when a bad job is reported (PF_ERR_BAD_ARG / PF_ERR_BAD_SHAPE), the launches before its own
+ * -- the first 16 jobs for a bad job at index 17 -- have already been enqueued, and no job of its own launch or after it has. */
 typedef struct pf_pack_job {
     const float* w0; const float* w1; const float* b0; const float* b1; void* dst_w; float* dst_b;
     int cout0, cout1, cin, kh, kw, mode, cin_rot, cout_pad, cin_pad;
@@ -574,7 +576,11 @@ int pf_space_to_depth2(const float* in, int C, float* out, int ld_out, int B, in
 /* Per-pixel EPE (evaluate.py:265 `torch.sum((flow - flow_gt)**2, dim=0).sqrt()`) and SEPE
  * (core/utils/spherical.py:20-53 `calculate_great_circle_distance`, R = 1; cosine = 0: method 'Haversine', the one
  * evaluate.py uses; cosine = 1: method 'Cosine', arccos of the spherical law of cosines as written at :40-46) of
- * pred vs gt, both NCHW [B,2,H,W].  epe / sd: [B,H,W]; either may be NULL. */
+ * pred vs gt, both NCHW [B,2,H,W].  epe / sd: [B,H,W]; either may be NULL.
+ * The haversine is clamped to [0, 1] before asin(sqrt(.)) and the cosine to [-1, 1] before acos(.): fp32 rounding takes them
+ * past 1 for antipodal resp. coincident end points (a perfect prediction in the Cosine form), where the reference's fp32
+ * spherical.py:80-84 returns NaN -- a deliberate departure, as in pf_fb_check and pf_flow_render: an antipodal or a
+ * coincident end point never gives NaN.  The clamp is two comparisons: a NaN input still gives NaN. */
 int pf_flow_metrics(const float* pred, const float* gt, float* epe, float* sd, int cosine, int B, int H, int W,
                     void* stream);
 

@@ -1304,10 +1304,14 @@ PF_HD void pf_flow_metrics_elem(long idx, const PfFlowMetricsArgs& a) {   // idx
         pf_endpoint_sph(x, y, pu, pv, a.H, a.W, tp, pp);
         pf_endpoint_sph(x, y, gu, gv, a.H, a.W, tg, pg);
         if (a.cosine) {         // method='Cosine' (core/utils/spherical.py:40-46): spherical law of cosines, as written there
-            const float ca = sinf(pp) * sinf(pg) + (cosf(pp) * cosf(pg)) * cosf(tg - tp);
+            // fp32 rounding takes cos(alpha) of coincident end points past 1 and the haversine of antipodal ones past 1 (a few
+            // per cent of the pixels of such a map): clamped like pf_fb_dist, with comparisons so that a NaN stays a NaN
+            float ca = sinf(pp) * sinf(pg) + (cosf(pp) * cosf(pg)) * cosf(tg - tp);
+            ca = ca < -1.f ? -1.f : (ca > 1.f ? 1.f : ca);
             a.sd[idx] = acosf(ca);
         } else {
-            const float hv = pf_haversine(pg - pp) + (cosf(pp) * cosf(pg)) * pf_haversine(tg - tp);
+            float hv = pf_haversine(pg - pp) + (cosf(pp) * cosf(pg)) * pf_haversine(tg - tp);
+            hv = hv < 0.f ? 0.f : (hv > 1.f ? 1.f : hv);
             a.sd[idx] = 2.f * asinf(sqrtf(hv));
         }
     }

@@ -11,7 +11,11 @@ Mirrors, with the reference's names and argument meaning:
 Differences that are deliberate: the datasets do not exist offline, so ``validate_regions`` takes any
 iterable of ``(image1, image2, flow_gt[, valid])`` samples; the model runs ONCE per sample (the
 reference re-runs it for every region, evaluate.py:245-263) and all regions are reduced by one kernel
-pass; ``validate_FlowScape_regions``' unpacking bug (evaluate.py:300) is not reproduced.
+pass; ``validate_FlowScape_regions``' unpacking bug (evaluate.py:300) is not reproduced; ``pf_flow_metrics``
+clamps the haversine to [0, 1] and the cosine of the 'Cosine' form to [-1, 1] before the inverse, where the
+reference's fp32 ``asin(sqrt(.))`` / ``arccos(.)`` (core/utils/spherical.py:80-84, :46) return NaN for antipodal
+resp. coincident end points that rounding takes past 1 -- one such pixel would turn a whole validation mean into
+NaN (a NaN flow still gives NaN).
 Per-pixel metrics and region sums run on the GPU (``pf_flow_metrics`` / ``pf_region_sums``); there is
 no CPU fallback.
 """

@@ -100,6 +100,78 @@ def test_null_and_shape_errors_are_reported_without_a_gpu(built_lib):
     assert dll.pf_adamw_step_dev(buf[0], buf[1], buf[2], buf[3], L(8), Fl(1.0), Fl(0.999), Fl(1e-8), buf[4], None) == -2
 
 
+def test_io_launch_refusals_need_no_gpu(built_lib):
+    """The refusals of the evaluation, weight-traffic and layout entry points (tests/io_launches.py runs their launches): every one
+    answers before anything is launched.  -1 = PF_ERR_BAD_ARG, -2 = PF_ERR_BAD_SHAPE."""
+    from prior_flow_amd import _lib
+    d = _lib.PfLib(built_lib, require_cuda=False)._dll
+    f = [ctypes.cast((ctypes.c_float * 64)(), ctypes.c_void_p) for _ in range(8)]
+    # pf_flow_metrics: both outputs NULL; B, H or W below 1
+    assert d.pf_flow_metrics(f[0], f[1], None, None, 0, 1, 4, 4, None) == -1
+    for B, H, W in ((0, 4, 4), (1, 0, 4), (1, 4, 0)):
+        assert d.pf_flow_metrics(f[0], f[1], f[2], f[3], 0, B, H, W, None) == -2
+    # pf_region_sums: nregions 0 and 9, nblk 0 and 4097, a NULL operand
+    for R, nblk in ((0, 4), (9, 4), (3, 0), (3, 4097)):
+        assert d.pf_region_sums(f[0], f[1], f[2], f[3], R, f[4], nblk, 1, 16, None) == -2
+    for i in (0, 1, 3, 5):                              # epe, sd, bits, partials (the weight may be NULL)
+        a = [f[0], f[1], f[2], f[3], 3, f[4], 4, 1, 16, None]
+        a[i] = None
+        assert d.pf_region_sums(*a) == -1
+
+    def pack(cout0=4, w1=None, cout1=0, cin=8, kh=3, kw=3, mode=0, rot=0, cout_pad=128, cin_pad=32):
+        return d.pf_pack_conv_weights(f[0], cout0, w1, cout1, None, None, cin, kh, kw, mode, rot, f[1], None, cout_pad, cin_pad, None)
+
+    assert pack(rot=8) == -2                            # cin_rot == cin
+    assert pack(kh=8) == -2
+    assert pack(cin_pad=48) == -2                       # cin_pad % 32 != 0
+    assert pack(cout_pad=3) == -2                       # mode 0: fewer rows than cout
+    assert pack(cin=40, cin_pad=32) == -2               # mode 0: fewer columns than cin
+    assert pack(mode=1, cout_pad=7) == -2               # mode 1: the rows are the forward cin
+    assert pack(mode=1, cout0=40, cout_pad=8, cin_pad=32) == -2       # mode 1: the columns are the forward cout
+    assert pack(cout1=4) == -1                          # cout1 > 0 with w1 NULL
+    assert d.pf_pack_conv_weights_batch((_lib.PackJob * 1)(), 0, None) == -1
+    assert d.pf_pack_conv_weights_batch(None, 3, None) == -1
+
+    def unpack(**kw):
+        q = _lib.UnpackJob()
+        q.dw, q.db, q.gw, q.gb = f[0], f[1], f[2], f[3]
+        q.cout, q.cin, q.taps, q.cin_pad, q.o_off, q.scale = 2, 3, 1, 32, 0, 1.0
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return d.pf_unpack_wgrads((_lib.UnpackJob * 1)(q), 1, None)
+
+    assert unpack(db=None) == -1                        # gb without db
+    assert unpack(cin=40) == -2                         # cin_pad < cin
+    # pf_to_channel_last: a slice past ld_out, act == 3, in == out; pf_space_to_depth2: an odd H
+    assert d.pf_to_channel_last(f[0], 8, 0, 4, f[1], 8, 5, 0, 1, 2, None) == -1
+    assert d.pf_to_channel_last(f[0], 8, 0, 4, f[1], 8, 0, 3, 1, 2, None) == -1
+    assert d.pf_to_channel_last(f[0], 8, 0, 4, f[0], 8, 0, 0, 1, 2, None) == -1
+    assert d.pf_space_to_depth2(f[0], 1, f[1], 4, 1, 3, 4, None) == -2
+
+
+def test_a_bad_pack_job_stops_the_batch_after_the_launches_before_it():
+    """pf_pack_conv_weights_batch validates the jobs of one launch (16) before that launch: a bad job at index 17 is reported when
+    the first 16 jobs have already been enqueued (include/priorflow_hip.h says so), and nothing of the second launch is.  Through the
+    host emulation, where an enqueued launch has run when the call returns."""
+    import numpy as np
+
+    import emu_lib
+    from prior_flow_amd import _lib
+    lib = emu_lib.load()
+    n = 20
+    w = torch.arange(2 * 3, dtype=torch.float32).reshape(2, 3, 1, 1) + 1
+    dst = [torch.full((1 * 1 * 32 * 2 * 2,), 0x7FC0, dtype=torch.int16) for _ in range(n)]
+    arr = (_lib.PackJob * n)()
+    for j, q in enumerate(arr):
+        q.w0, q.dst_w = w.data_ptr(), dst[j].data_ptr()
+        q.cout0, q.cout1, q.cin, q.kh, q.kw, q.mode, q.cin_rot, q.cout_pad, q.cin_pad = 2, 0, 3, 1, 1, 0, 0, 2, 32
+    arr[17].cin_rot = 3                                 # == cin
+    assert lib._dll.pf_pack_conv_weights_batch(arr, n, None) == -2
+    written = [not bool((t == 0x7FC0).all()) for t in dst]
+    assert written == [True] * 16 + [False] * 4
+    assert np.array_equal(dst[0].numpy().view(np.uint16)[:3], (w[0, :, 0, 0].numpy().view(np.uint32) >> 16).astype(np.uint16))
+
+
 def test_conv_launch_plan_is_host_logic(built_lib, monkeypatch):
     """pf_conv2d_tile / pf_conv2d_stats_blocks launch nothing and need no GPU: which kernel a convolution takes and how many
     statistics partials it writes is host arithmetic over the descriptor.  Round 5's weights-stationary encoder kernel (tile code
