@@ -174,6 +174,48 @@ int pf_augment_convert(const unsigned char* in, unsigned char* out, long n, int 
 int pf_masked_mean(const float* x, const unsigned char* mask, float* out, void* scratch, long scratch_bytes, int B, int N,
                    void* stream);
 
+/* Perspective viewports and cube maps of ERP frames and ERP flow.  Geometry, the reference's convention
+ * (core/utils/projection_prim_ortho.py:264-430; its diverge_zero nudge is not applied):
+ *   ERP pixel (m, n): theta = ((m + 1/2) / W - 1/2) 2 pi, phi = (1/2 - (n + 1/2) / H) pi, s(m, n) = (cos phi cos theta,
+ *   cos phi sin theta, sin phi); a direction d lies at theta = atan2(d_y, d_x), phi = asin(d_z / |d|),
+ *   m = (theta / 2 pi + 1/2) W - 1/2, n = (1/2 - phi / pi) H - 1/2.
+ *   A view is (R, f, h, w): R 3x3 with columns forward, right, up in world axes, f the focal length in pixels, principal point
+ *   (c_x, c_y) = ((w - 1) / 2, (h - 1) / 2).  Pixel (i, j) has the camera ray (1, (j - c_x) / f, -(i - c_y) / f) and the world
+ *   ray d = R ray; proj(q) = (c_x + f q_r / q_f, c_y - f q_u / q_f), (q_f, q_r, q_u) = R^T q.  With R = I the view looks at the
+ *   ERP centre, right is +m and down is +n.
+ * views_host: V rows of PF_VIEW_WORDS HOST floats {R row-major, f, h, w}, 1 <= V <= PF_VIEW_MAX, every row with the same h x w;
+ * the table travels to the kernel as an argument (no copy to the device, the call can be captured; a captured call keeps the
+ * table it was captured with).  One thread per output pixel; ray, position and taps are computed once for all channels.
+ * Every entry: one launch, no host read, no allocation.  PF_ERR_BAD_ARG: a NULL pointer, an output aliasing an input or the other
+ * output, an R entry or f that is not finite, f <= 0, an unknown form, min_forward outside (0, 1).  PF_ERR_BAD_SHAPE: V outside
+ * 1..PF_VIEW_MAX, h or w that is no integer in 1..32768 or differs between rows, B, C, H, W or s < 1, C > 4096, H * W or
+ * h * w >= 2^30, B * V > 65535 (an image of a view is one row of the launch grid).
+ *
+ * pf_viewport_image: ERP -> views, sampled at the ray's (m, n) with the model's cyclic taps (x wraps, y clamps, weights from the
+ *   unclamped fraction: rays towards a pole read the pole row).  PF_VIEW_F32: in [B,C,H,W] fp32 -> out [B,V,C,h,w] fp32;
+ *   PF_VIEW_U8: in [B,H,W,C] bytes (what pf_flow_render writes) -> out [B,V,h,w,C] bytes, floor(x + 1/2) clamped to 0..255.
+ *   No anti-aliasing: a view coarser than the panorama is point-sampled with four taps.
+ * pf_viewport_flow: ERP flow [B,2,H,W] -> pinhole flow out [B,V,2,h,w] (view pixels; channel 0 along j, 1 along i) and valid
+ *   [B,V,h,w] bytes.  For the pixel's unit ray p^ and the four taps k (weights w_k) of its position: s_k = s(m_k, n_k),
+ *   e_k = s(m_k + u_k, clamp(n_k + v_k, -1/2, H - 1/2)) (flow2endpoint's rule), q = p^ + sum w_k (e_k - s_k),
+ *   out = proj(q) - proj(p^).  The 3-D displacement is interpolated, never u or v: the seam needs no un-wrapping, a zero flow
+ *   gives exactly (0, 0), and the result is second-order accurate in the pixel pitch.  valid = 1 exactly when the flows of all
+ *   four taps are finite and q_f > min_forward |q| (the default of the Python layer: cos 85 deg); where valid = 0 out is (0, 0).
+ *   Every read stays inside the maps for any input bits.
+ * pf_cubemap_to_erp: faces [B,6,C,s,s] fp32 -> out [B,C,H,W].  Faces in the order front, right, back, left, up, down with R columns
+ *   [forward, right, up] = [+x +y +z], [+y -x +z], [-x -y +z], [-y +x +z], [+z +y -x], [-z +y +x] and f = s / 2.  Per ERP pixel
+ *   d = s(m, n); the face is the axis with the largest |component| (ties: the earlier face); bilinear at proj(d) with the taps
+ *   clamped to that face.  No filtering across face edges. */
+#define PF_VIEW_MAX 16
+#define PF_VIEW_WORDS 12
+#define PF_VIEW_F32 0
+#define PF_VIEW_U8 1
+int pf_viewport_image(const void* in, void* out, const float* views_host, int V, int B, int C, int H, int W, int form,
+                      void* stream);
+int pf_viewport_flow(const float* flow, const float* views_host, int V, float* out, unsigned char* valid, int B, int H, int W,
+                     float min_forward, void* stream);
+int pf_cubemap_to_erp(const float* faces, float* out, int B, int C, int s, int H, int W, void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

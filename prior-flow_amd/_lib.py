@@ -163,12 +163,18 @@ _SIGNATURES = {
     "pf_augment_scratch_bytes": [_i],
     "pf_augment_360": [_fp] * 9 + [C.c_long, _i, _i, _i, _fp],
     "pf_augment_convert": [_fp, _fp, C.c_long, _i, _fp],
+    "pf_viewport_image": [_fp, _fp, C.POINTER(C.c_float), _i, _i, _i, _i, _i, _i, _fp],
+    "pf_viewport_flow": [_fp, C.POINTER(C.c_float), _i, _fp, _fp, _i, _i, _i, C.c_float, _fp],
+    "pf_cubemap_to_erp": [_fp, _fp, _i, _i, _i, _i, _i, _fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
-# entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp): a host-only handle
-# (require_cuda=False) may lack them and then refuses the call; the product's handle never may
-_OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert")
+# entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp): a host-only
+# handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+_OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert",
+                  "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp")
 AUG_ROW_WORDS = 32                                  # PF_AUG_ROW_WORDS
+VIEW_MAX, VIEW_WORDS = 16, 12                       # PF_VIEW_MAX, PF_VIEW_WORDS
+VIEW_F32, VIEW_U8 = 0, 1                            # PF_VIEW_F32 / PF_VIEW_U8
 
 
 class PfError(RuntimeError):
@@ -1047,6 +1053,61 @@ class PfLib:
             raise PfError(f"augment_convert: src {tuple(src.shape)} / out {tuple(out.shape)}, expected equal shapes [..., 3]")
         self._rc(self._dll.pf_augment_convert(_ptr(src), _ptr(out), src.numel() // 3, int(bool(to_rgb)), self._stream(src)),
                  "pf_augment_convert")
+        return out
+
+    # ---- perspective viewports and cube maps ---------------------------
+    @staticmethod
+    def view_table(rows):
+        """The host table of pf_viewport_*: V rows {R row-major, f, h, w} as a ctypes float array (built once per view set)."""
+        rows = [[float(v) for v in r] for r in rows]
+        if not 1 <= len(rows) <= VIEW_MAX or any(len(r) != VIEW_WORDS for r in rows):
+            raise PfError(f"a view table has 1..{VIEW_MAX} rows of {VIEW_WORDS} numbers")
+        return (C.c_float * (len(rows) * VIEW_WORDS))(*[v for r in rows for v in r])
+
+    def viewport_image(self, x, table, out):
+        """ERP -> views (pf_viewport_image): x fp32 [B,C,H,W] -> out [B,V,C,h,w], or uint8 [B,H,W,C] -> out [B,V,h,w,C]."""
+        self._have("pf_viewport_image")
+        V = len(table) // VIEW_WORDS
+        h, w = int(table[10]), int(table[11])
+        if x.dim() != 4 or x.dtype not in (torch.float32, torch.uint8) or out.dtype != x.dtype:
+            raise PfError(f"viewport_image: x {x.dtype} {tuple(x.shape)} / out {out.dtype}, expected fp32 [B,C,H,W] or uint8 [B,H,W,C]")
+        self._chk_bytes(x, "viewport_image: x")
+        self._chk_bytes(out, "viewport_image: out")
+        if x.dtype == torch.float32:
+            (B, Cc, H, W), form, want = x.shape, VIEW_F32, lambda: (B, V, Cc, h, w)
+        else:
+            (B, H, W, Cc), form, want = x.shape, VIEW_U8, lambda: (B, V, h, w, Cc)
+        if tuple(out.shape) != want():
+            raise PfError(f"viewport_image: out {tuple(out.shape)}, expected {want()} for x {tuple(x.shape)}")
+        self._rc(self._dll.pf_viewport_image(_ptr(x), _ptr(out), table, V, B, Cc, H, W, form, self._stream(x)), "pf_viewport_image")
+        return out
+
+    def viewport_flow(self, flow, table, out, valid, min_forward: float):
+        """ERP flow [B,2,H,W] -> pinhole flow out [B,V,2,h,w] and valid uint8 [B,V,h,w] (pf_viewport_flow)."""
+        self._have("pf_viewport_flow")
+        V = len(table) // VIEW_WORDS
+        h, w = int(table[10]), int(table[11])
+        self._chk(flow, out)
+        self._chk_bytes(valid, "viewport_flow: valid", torch.uint8)
+        if flow.dim() != 4 or flow.shape[1] != 2:
+            raise PfError(f"viewport_flow: flow {tuple(flow.shape)}, expected [B,2,H,W]")
+        B, _, H, W = flow.shape
+        if tuple(out.shape) != (B, V, 2, h, w) or tuple(valid.shape) != (B, V, h, w):
+            raise PfError(f"viewport_flow: out {tuple(out.shape)} / valid {tuple(valid.shape)}, expected {(B, V, 2, h, w)} and {(B, V, h, w)}")
+        self._rc(self._dll.pf_viewport_flow(_ptr(flow), table, V, _ptr(out), _ptr(valid), B, H, W, float(min_forward),
+                                            self._stream(flow)), "pf_viewport_flow")
+        return out, valid
+
+    def cubemap_to_erp(self, faces, out):
+        """Cube faces [B,6,C,s,s] -> ERP out [B,C,H,W] (pf_cubemap_to_erp)."""
+        self._have("pf_cubemap_to_erp")
+        self._chk(faces, out)
+        if faces.dim() != 5 or faces.shape[1] != 6 or faces.shape[3] != faces.shape[4] or out.dim() != 4 \
+                or out.shape[0] != faces.shape[0] or out.shape[1] != faces.shape[2]:
+            raise PfError(f"cubemap_to_erp: faces {tuple(faces.shape)} / out {tuple(out.shape)}, expected [B,6,C,s,s] and [B,C,H,W]")
+        B, Cc, H, W = out.shape
+        self._rc(self._dll.pf_cubemap_to_erp(_ptr(faces), _ptr(out), B, Cc, faces.shape[3], H, W, self._stream(faces)),
+                 "pf_cubemap_to_erp")
         return out
 
     def masked_mean(self, x, mask, out, scratch):
