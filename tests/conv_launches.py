@@ -9,6 +9,8 @@ test_conv_launch_reference.py; not a conftest).
                                      the columns a launch may write), descriptors ready for lib.conv2d.
   reference(case)                    the same convolutions in float64 with per-element error bounds (see TOLERANCES).
   check_case(case, ref)              compares every output form, the fused statistics and the sentinels; returns failures.
+  relation / reachable / witness     the plans a recorded layout reaches over the image sizes and batches the product supports
+                                     (GRID), and the geometry at which to replay each of them.  Host logic only.
 
 TOLERANCES.  For one output element v = b + sum_k x_k w_k (+ pre) let
     A = sum_k |x_k w_k| + |b| + |pre|        (what a worst-case rounding analysis multiplies)
@@ -135,14 +137,16 @@ class Launch:
     W: int
     groups: List[dict]
     path: str = ""
+    image: tuple = None                # (B_img, H_img, W_img) of the product run the launch was recorded in
 
 
 class Recorder(contextlib.AbstractContextManager):
     """Wraps PfLib.conv2d on the class: every launch is recorded, then runs as before.  Enter it before the model or
     engine is built (a bound method cached by one of them would otherwise escape)."""
 
-    def __init__(self, path: str = ""):
+    def __init__(self, path: str = "", image: tuple = None):
         self.path = path
+        self.image = image             # the image geometry (B, H, W) of the path being recorded (see relation)
         self.launches: List[Launch] = []
 
     def __enter__(self):
@@ -153,7 +157,7 @@ class Recorder(contextlib.AbstractContextManager):
 
         def conv2d(lib, descs, B, H8, W8, like):
             groups = [_layout(d) for d in descs]
-            rec.launches.append(Launch(signature_of_layouts(plan(lib, list(descs), B, H8, W8), groups), B, H8, W8, groups, rec.path))
+            rec.launches.append(Launch(signature_of_layouts(plan(lib, list(descs), B, H8, W8), groups), B, H8, W8, groups, rec.path, rec.image))
             return orig(lib, descs, B, H8, W8, like)
 
         self._cls.conv2d = conv2d
@@ -673,3 +677,84 @@ def why_no_sibling(lib, launch: Launch) -> str:
     if any(g["has_stats_out"] for g in launch.groups) and launch.sig[3] in ("tile0", "tile1", "tile2", "tile7"):
         return "fused statistics on the generic kernel need H*W % BM == 0"
     return "no candidate near the product geometry keeps the signature (tile / roles choice depends on the work-item count)"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the plans a layout reaches
+# ---------------------------------------------------------------------------------------------------------------------
+# Image geometries the product is run at by a test, the bench or DESIGN.md (1920x3840: the panorama of section 10); a
+# bidirectional stream doubles B, which the batches below cover.
+GRID_SIZES = ((128, 256), (136, 216), (160, 360), (256, 512), (384, 512), (480, 960), (512, 1024), (640, 1280), (1024, 2048),
+              (1920, 3840))
+GRID_BATCHES = (1, 2, 3, 4, 8, 16, 32)
+GRID = tuple((B, H, W) for H, W in GRID_SIZES for B in GRID_BATCHES)
+
+
+def relation(launch: Launch):
+    """(m, d) of a recorded launch: m = launch.B / B_img images per pair the layer sees (2 frames, 4 with the rotated
+    ones, ...), d = H_img / launch.H = W_img / launch.W the layer's resolution divisor.  Both are positive integers in
+    every layer of the model; anything else is an error that names the launch."""
+    if not launch.image:
+        raise ValueError(f"launch without the image geometry of its path: {sig_str(launch.sig)}")
+    Bi, Hi, Wi = launch.image
+    ok = min(Bi, Hi, Wi, launch.B, launch.H, launch.W) > 0 and launch.B % Bi == 0 and Hi % launch.H == 0 and \
+        Wi % launch.W == 0 and Hi // launch.H == Wi // launch.W
+    if not ok:
+        raise ValueError(f"launch {launch.B}x{launch.H}x{launch.W} in a path of {Bi}x{Hi}x{Wi} images is no whole number of "
+                         f"images per pair at a whole resolution divisor: {sig_str(launch.sig)}")
+    return launch.B // Bi, Hi // launch.H
+
+
+def _desc_array(descs):
+    return (type(descs[0]) * len(descs))(*descs)
+
+
+def reachable(lib, launch: Launch, grid=GRID) -> Dict[tuple, List[tuple]]:
+    """{signature: [launch geometry (B, H, W), ...]} of every plan the planner gives the layout of `launch` over the image
+    geometries of `grid`: an image geometry (B, H, W) is the launch geometry (m B, H / d, W / d) with relation(launch)'s
+    (m, d); sizes d does not divide, geometries the planner refuses and launches with stats_out the planner gives no
+    statistics blocks (the rule of same_signature) are left out.  The launch's own signature is among the keys when the
+    grid holds its image geometry.
+
+    The layout is held fixed while the geometry moves.  That over-approximates what the product reaches: the engine may
+    build another layout at another size (fp32 rows instead of twins, a separate statistics pass, another co_groups), so a
+    signature found here need not be one the product launches.  A plan the product never takes costs its replay a few
+    seconds; a plan it takes that nobody checked costs a wrong flow."""
+    m, d = relation(launch)
+    descs = fake_descs(launch)
+    arr = _desc_array(descs)
+    stats = any(g["has_stats_out"] for g in launch.groups)
+    out: Dict[tuple, List[tuple]] = {}
+    for Bi, Hi, Wi in grid:
+        if Hi % d or Wi % d:
+            continue
+        geo = (m * Bi, Hi // d, Wi // d)
+        tr = plan(lib, descs, *geo)
+        if tr[0] < 0 or tr[1] < 0:
+            continue
+        if stats and int(lib._dll.pf_conv2d_stats_blocks(arr, len(descs), *geo)) <= 0:
+            continue
+        geos = out.setdefault(signature_of_layouts(tr, launch.groups), [])
+        if geo not in geos:
+            geos.append(geo)
+    return out
+
+
+def with_signature(launch: Launch, sig, B, H, W) -> Launch:
+    """The launch's layout under another plan and geometry (what same_signature and ragged_sibling compare against)."""
+    return Launch(sig, B, H, W, launch.groups, launch.path, launch.image)
+
+
+def witness(lib, launch: Launch, sig, geos, ragged: bool = True):
+    """The geometry at which to replay signature `sig` of the layout of `launch`, out of reachable()'s `geos`:
+    (B, H, W, was_made_ragged).  The candidate with the fewest output pixels x groups (ties: H odd or W no multiple of 32
+    first), then -- unless `ragged` is False -- its ragged sibling (B >= 2, H and W odd, near the candidate's size) where
+    the planner keeps the signature there."""
+    ng = len(launch.groups)
+    B, H, W = min(geos, key=lambda g: (g[0] * g[1] * g[2] * ng, 0 if (g[1] % 2 or g[2] % 32) else 1, g))
+    if ragged:
+        probe = with_signature(launch, sig, B, H, W)
+        sib = ragged_sibling(lib, probe)
+        if sib is not None and same_signature(lib, probe, *sib):
+            return sib + (True,)
+    return B, H, W, False

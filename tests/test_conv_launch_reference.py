@@ -1,5 +1,5 @@
 """CPU checks of tests/conv_launches.py, the harness of test_hip_conv_launches.py: the launch signature and the ragged-geometry
-search on the built library's host planners (fake pointers, as in test_abi.py), and proof that the float64 reference's error
+search and the enumeration of reachable plans on the built library's host planners (fake pointers, as in test_abi.py), and proof that the float64 reference's error
 bounds have teeth -- emulated wrong kernels fail them, the exact result passes with margin.  No GPU."""
 import math
 
@@ -38,8 +38,8 @@ def _desc(cin, cout, kh, kw, prec=1, split=False, epi=0, **kw_):
     return d
 
 
-def _launch(lib, descs, B, H, W):
-    return cl.Launch(cl.signature(lib, descs, B, H, W), B, H, W, [cl._layout(d) for d in descs], "test")
+def _launch(lib, descs, B, H, W, image=None):
+    return cl.Launch(cl.signature(lib, descs, B, H, W), B, H, W, [cl._layout(d) for d in descs], "test", image)
 
 
 # one launch per planner outcome: (descriptor arguments, geometry, tile, roles)
@@ -122,6 +122,92 @@ def test_tile6_has_no_ragged_sibling_and_says_why(lib):
     assert launch.sig[3] == "tile6"
     assert cl.ragged_sibling(lib, launch) is None
     assert "32-column" in cl.why_no_sibling(lib, launch)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the plans a layout reaches over the supported geometries
+# ---------------------------------------------------------------------------------------------------------------------
+def _f16_zr():
+    """The f16 GRU z|r convolution as the update block launches it: 1x5, 256 -> 256, two groups, r*h into an f16 map."""
+    zr = dict(cin=256, cout=256, kh=1, kw=5, prec=2, epi=2, h=2 * FAKE, ld_h=128, ld_out=128, aux_split=FAKE, lds_aux=2)
+    return [_desc(**zr), _desc(**zr)]
+
+
+def _plans(reach):
+    return {(s[3], s[4]) for s in reach}
+
+
+@pytest.mark.parametrize("B", [1, 32])
+def test_reachable_finds_the_small_map_plans_of_the_f16_gru(lib, B):
+    launch = _launch(lib, _f16_zr(), B, 64, 128, image=(B, 512, 1024))
+    assert cl.relation(launch) == (1, 8)
+    assert launch.sig[0] == "f16" and launch.sig[3:5] == ("tile4", "roles18")
+    reach = cl.reachable(lib, launch)
+    assert reach == cl.reachable(lib, launch)                                      # deterministic, lists in grid order
+    assert launch.sig in reach and (launch.B, launch.H, launch.W) in reach[launch.sig]
+    assert {("tile4", "roles18"), ("tile3", "roles17"), ("tile3", "roles18")} <= _plans(reach), _plans(reach)
+    for sig, geos in reach.items():
+        assert sig[:3] + sig[5:] == launch.sig[:3] + launch.sig[5:]                # only the plan moves
+        assert len(set(geos)) == len(geos)
+        for ragged in (False, True):
+            b, h, w, made = cl.witness(lib, launch, sig, geos, ragged=ragged)
+            assert cl.same_signature(lib, cl.with_signature(launch, sig, b, h, w), b, h, w), (sig, b, h, w)
+            assert made == (ragged and (b, h, w) not in geos)
+            if made:
+                assert b >= 2 and h % 2 and w % 2
+    small = next(s for s in reach if s[3:5] == ("tile3", "roles17"))
+    b, h, w, made = cl.witness(lib, launch, small, reach[small], ragged=False)
+    assert not made and b * h * w <= 1 * 16 * 32, (b, h, w)
+    mid = next(s for s in reach if s[3:5] == ("tile3", "roles18"))
+    assert (1, 60, 120) in reach[mid]                                              # one 480 x 960 pair
+
+
+def test_reachable_finds_the_8_row_halo_tile_of_encoder_layer_1(lib):
+    """3x3 64 -> 64 on fp32 rows, four images per pair at half resolution: the weights-stationary kernel (tile 6) at
+    512 x 1024, the 8-row halo kernel (tile 5) where the half-resolution width is no multiple of 32."""
+    launch = _launch(lib, [_desc(64, 64, 3, 3)], 4, 256, 512, image=(1, 512, 1024))
+    assert cl.relation(launch) == (4, 2) and launch.sig[3] == "tile6"
+    reach = cl.reachable(lib, launch)
+    assert reach == cl.reachable(lib, launch)
+    t5 = [s for s in reach if s[3] == "tile5"]
+    assert len(t5) == 1 and all(h % 8 or w % 32 for _, h, w in reach[t5[0]]), t5
+    assert (16, 68, 108) in reach[t5[0]] and (12, 80, 180) in reach[t5[0]]         # 4 x 136 x 216, 3 x 160 x 360
+    assert all(w % 32 == 0 and h % 8 == 0 for s in reach if s[3] == "tile6" for _, h, w in reach[s])
+    b, h, w, made = cl.witness(lib, launch, t5[0], reach[t5[0]])
+    assert cl.same_signature(lib, cl.with_signature(launch, t5[0], b, h, w), b, h, w)
+    assert made and b >= 2 and h % 8 and w % 32
+    # with the fused statistics the blocks rule of same_signature applies and the witness keeps them
+    st = _launch(lib, [_desc(64, 64, 3, 3, stats_out=FAKE, in_scale=FAKE, in_shift=FAKE, in_relu=1)], 4, 256, 512, image=(1, 512, 1024))
+    reach = cl.reachable(lib, st)
+    t5 = [s for s in reach if s[3] == "tile5"]
+    assert len(t5) == 1
+    b, h, w, made = cl.witness(lib, st, t5[0], reach[t5[0]])
+    assert cl.same_signature(lib, cl.with_signature(st, t5[0], b, h, w), b, h, w)
+
+
+def test_reachable_drops_sizes_the_divisor_does_not_divide_and_refusals(lib):
+    launch = _launch(lib, [_desc(256, 128, 3, 3, split=True)], 1, 17, 27, image=(1, 136, 216))
+    assert cl.relation(launch) == (1, 8)
+    reach = cl.reachable(lib, launch, grid=((1, 136, 216), (1, 100, 216), (1, 136, 220), (2, 512, 1024)))
+    assert sorted(g for geos in reach.values() for g in geos) == [(1, 17, 27), (2, 64, 128)]
+    # fused statistics on the generic kernel exist only where its pixel tiles do not straddle images: other sizes are left out
+    st = _launch(lib, [_desc(64, 96, 3, 3, stride=2, stats_out=FAKE)], 4, 128, 256, image=(1, 512, 1024))
+    assert st.sig[3] == "tile7"
+    for sig, geos in cl.reachable(lib, st).items():
+        for b, h, w in geos:
+            assert cl.same_signature(lib, cl.with_signature(st, sig, b, h, w), b, h, w)
+    assert all(g != (4, 34, 54) for geos in cl.reachable(lib, st).values() for g in geos)     # 34 * 54 % 128 != 0
+
+
+def test_relation_needs_whole_images_and_a_whole_divisor(lib):
+    d = [_desc(256, 128, 3, 3, split=True)]
+    assert cl.relation(_launch(lib, d, 6, 64, 128, image=(3, 512, 1024))) == (2, 8)
+    for geo, image in (((3, 64, 128), (2, 512, 1024)), ((1, 64, 128), (1, 500, 1024)), ((1, 64, 128), (1, 512, 512)),
+                       ((1, 64, 128), (2, 512, 1024)), ((1, 64, 128), None)):
+        launch = _launch(lib, d, *geo, image=image)
+        with pytest.raises(ValueError) as e:
+            cl.relation(launch)
+        assert cl.sig_str(launch.sig) in str(e.value)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -276,3 +362,83 @@ def test_reference_is_float64_conv2d():
         absw = torch.nn.functional.conv2d(xn.abs(), w.abs(), stride=s)[:, :, :H, :W].permute(0, 2, 3, 1).reshape(-1, cout)
         assert torch.allclose(got["abs"], absw, rtol=1e-12, atol=1e-12)
         assert math.isclose(float(got["sq"].sum()), float(torch.nn.functional.conv2d(xn * xn, w * w, stride=s)[:, :, :H, :W].sum()), rel_tol=1e-12)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# ragged tiles of the 8-row halo kernel
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def tile5_case(lib):
+    """Encoder layer 1 as fnet launches it (3x3 64 -> 64 on fp32 rows, folded input norm + ReLU, fused statistics) on the
+    8-row halo tile at H = 13 (a 5-row last tile) and W = 41 (a 9-column last strip), with its exact result."""
+    B, H, W = 128, 13, 41
+    d = _desc(64, 64, 3, 3, in_scale=FAKE, in_shift=FAKE, in_relu=1, stats_out=FAKE)
+    launch = _launch(lib, [d], B, H, W)
+    assert launch.sig[3] == "tile5"
+    case = cl.build_case(lib, launch, B, H, W, torch.device("cpu"), seed=13)
+    return case, cl.reference(case)
+
+
+def _store(case, acc_of):
+    """Fills the case's buffers as a kernel would whose accumulators are acc_of(exact accumulators [B, H, W, cout]) -- NaN
+    marks a pixel it never writes (the sentinel stays) --, statistics partials consistent with what it wrote."""
+    g = case.groups[0]
+    T = g["T"]
+
+    def conv(x, w, B, H, W, stride):
+        r = dict(cl.conv_fp64(x, w, B, H, W, stride))
+        r["acc"] = acc_of(r["acc"].view(B, H, W, -1).clone()).reshape(B * H * W, -1)
+        return r
+    val = cl.reference(case, conv=conv)[0]["out"]["ref"]
+    out = torch.full_like(T["out"], cl.SENT_F32)
+    live = out[:, g["off_out"]:g["off_out"] + g["cout"]]
+    live.copy_(torch.where(torch.isnan(val), torch.full_like(val, cl.SENT_F32), val).float())
+    T["out"].copy_(out)
+    y = live.double().view(case.B, -1, g["cout"])
+    T["stats"].zero_()
+    T["stats"][:, 0, :, 0], T["stats"][:, 0, :, 1] = y.sum(1), (y * y).sum(1)
+
+
+def _nan_from(rows=None, cols=None):
+    def f(acc):
+        acc[:, rows if rows is not None else slice(None), cols if cols is not None else slice(None)] = float("nan")
+        return acc
+    return f
+
+
+def _stale_rows(acc):                           # the last tile's rows still hold the tile above
+    acc[:, 8:13] = acc[:, 0:5]
+    return acc
+
+
+def _stale_cols(acc):                           # the last strip's columns still hold the strip before
+    acc[:, :, 32:41] = acc[:, :, 0:9]
+    return acc
+
+
+def _zero_cols(acc):                            # the last strip's accumulators never saw a product: bias only
+    acc[:, :, 32:41] = 0
+    return acc
+
+
+def test_tile5_exact_result_passes(tile5_case):
+    case, refs = tile5_case
+    _store(case, lambda acc: acc)
+    fails, worst = cl.check_case(case, refs)
+    assert not fails, fails
+    assert worst["elem"] <= 0.05 and worst["agg"] <= 0.05, worst         # fp32 rounding of the stored value only
+
+
+@pytest.mark.parametrize("fault", [_nan_from(rows=slice(8, 13)), _stale_rows, _nan_from(cols=slice(32, 41)), _stale_cols, _zero_cols],
+                         ids=["last-row-tile-unwritten", "last-row-tile-stale", "last-strip-unwritten", "last-strip-stale", "last-strip-no-products"])
+def test_tile5_partial_tiles_have_teeth(tile5_case, fault):
+    """A kernel that loses the rows of the last partial 8-row tile or the columns of the last partial 32-column strip fails
+    check_case on the output itself (the statistics are kept consistent with what it stored)."""
+    case, refs = tile5_case
+    _store(case, fault)
+    fails, worst = cl.check_case(case, refs)
+    assert any("group 0 out" in f and "per-element" in f for f in fails), fails
+    assert any("group 0 out" in f and "aggregate" in f for f in fails), fails
+    assert worst["elem"] > 10 and worst["agg"] > 10, worst
+    _store(case, lambda acc: acc)                                         # leave the shared case exact
+    assert not cl.check_case(case, refs)[0]
