@@ -456,3 +456,13 @@ def test_design_numbers_are_the_committed_profiles():
     text = open(os.path.join(root, "DESIGN.md")).read()
     a, e = text.index(dn.BEGIN) + len(dn.BEGIN), text.index(dn.END)
     assert text[a:e].strip() == dn.build().strip(), "DESIGN.md's generated block is stale: python profiles/design_numbers.py --write"
+
+
+def test_design_state_table_is_the_audits_classification():
+    """DESIGN.md section 16 prints the classification of the resident buffers; the table there is the verbatim output of
+    tests/state_audit.py: design_table(), so the document and the audit the suite runs cannot drift apart."""
+    import state_audit as sa
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "DESIGN.md")).read()
+    a, e = text.index(sa.BEGIN) + len(sa.BEGIN), text.index(sa.END)
+    assert text[a:e].strip() == sa.design_table().strip(), "DESIGN.md's state table is stale: paste state_audit.design_table()"
