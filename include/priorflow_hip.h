@@ -502,7 +502,9 @@ int pf_conv2d(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8, voi
  * channels; 7 = round 6, for the 96 output channels of the encoders' layer 2); halo kernel 3: 128x64, 4: 128x128, 5: 256x64
  * (8-row tile), 8: 256x96 (8-row tile, 3x3 with 64 < Cout <= 96; round 6); 6: the weights-stationary kernel of the encoders'
  * 3x3 64 -> 64 convolutions (round 5; core/extractor.py:16-17 at 1/2 resolution: strips of 32 columns walked in 4-row steps,
- * outputs bit-identical to tile 5).  Lets a profiler attribute measured time to the right kernel instantiation. */
+ * outputs bit-identical to tile 5).  A 3x3 launch of the all-DMA kernel (pf_conv2d_roles >= 16) on tiles 3 / 4 reports the
+ * channel half of its tile here -- 3: NT = 1, 4: NT = 2 (32 * NT channels per MFMA wave) -- and the pixel half in the roles
+ * code.  Lets a profiler attribute measured time to the right kernel instantiation. */
 int pf_conv2d_tile(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8);
 
 /* pf_conv2d_stats_blocks: how many fp64 partial blocks PER IMAGE the launch writes to `stats_out` (the nblk of
@@ -515,7 +517,12 @@ int pf_conv2d_stats_blocks(const pf_conv_desc* descs, int ngroups, int B, int H8
  * 0: every wave stages and multiplies (pf_conv_halo_kernel), 1: four MFMA waves + four loader waves on the same tile
  * (pf_conv_ws_kernel<NT, KH, KW, 2>; tiles 3 / 4), 2: the same with a 256 px x 64 channel tile (pf_conv_ws_kernel<2, KH, KW, 1>;
  * tiles 3 / 4); 16 + 1 | 16 + 2: the launch has pre-split operands and takes the all-DMA kernel (pf_conv_dma_kernel) with
- * that tile (tiles 3, 4, 5, 8; tile 5 always with 16 + 2). */
+ * the 128-pixel | a 256-pixel tile (tiles 3, 4, 5, 8; tile 5 always with 16 + 2).  3x3 on tiles 3 / 4: the tile is the one whose
+ * busiest workgroup stages the fewest bytes, and the two codes name the instantiation --
+ * tile 3, 16 + 1: pf_conv_dma_kernel<1,3,3,2> 128 px x 64 channels;   tile 3, 16 + 2: <1,3,3,1> 256 px x 32 channels;
+ * tile 4, 16 + 1: <2,3,3,2> 128 px x 128 channels;                    tile 4, 16 + 2: <2,3,3,1> 256 px x 64 channels.
+ * (1x5 / 5x1, and every launch under PRIORFLOW_DMA_TALL=0 -- an A/B knob read once per process that restores the tile choice
+ * before that rule --, report 16 + 2 for <2,KH,KW,1> on whichever of the tiles 3 / 4 the work-item count gave.) */
 int pf_conv2d_roles(const pf_conv_desc* descs, int ngroups, int B, int H8, int W8);
 
 /* The encoders' first convolution (core/extractor.py:122, :144: conv1 7x7 stride 2 pad 3, 3 -> 64) straight from the NCHW

@@ -111,8 +111,61 @@ static bool roles_apply(const ConvGroups& grp, int ngroups, const ConvGeom& g) {
     return true;
 }
 
+// What one tile of pf_conv_dma_kernel<NT, ., ., WN> costs a launch -- the two numbers its tile choice is made of:
+//   items       work items of the launch: pixel tiles (TH = 8 / WN rows x 32 columns; a ragged map's partial tiles count as whole
+//               ones -- a 12-row map has two 8-row tiles, one of them half empty) x channel tiles of BN = 32 * NT * WN x groups
+//   step_bytes  bytes a workgroup stages L2 -> LDS per K-step (one tap of one 128-byte operand chunk): a weight tile of BN rows
+//               of 128 bytes, plus the chunk's halo -- (TH + kh - 1) x (32 + kw - 1) rows, rounded up to the 32-row pieces the
+//               loaders issue -- spread over its kh * kw taps.  3x3: <1,2> 11.1 KB, <1,1> 8.9, <2,2> 19.1, <2,1> 12.9
+// MFMA-busy is 0.09-0.15 on these launches, so a workgroup's time is taken as (items it walks) x (K-steps, the same on every
+// tile) x step_bytes.  Measured, that overstates what the bytes buy at NT = 1 (-20 % of the bytes: -5 % of the launch; DESIGN.md
+// section 6 has the table), but the order of the candidates it gives is the measured one.
+struct DmaTileCost { long items, step_bytes; };
+static DmaTileCost dma_tile_cost(const ConvGeom& g, int ngroups, int max_cout, int nt, int wn) {
+    const int th = 8 / wn, bn = 32 * nt * wn;
+    const long tiles = (long)(g.M / g.N) * ((g.H + th - 1) / th) * ((g.W + 31) / 32);
+    const long halo_rows = ((long)(th + g.kh - 1) * (32 + g.kw - 1) + 31) / 32 * 32;
+    return {tiles * ((max_cout + bn - 1) / bn) * ngroups, (long)bn * 128 + halo_rows * 128 / g.taps};
+}
+
+// The tile of a 3x3 all-DMA launch, as NT * 4 + WN: the one whose busiest workgroup stages the fewest bytes.  The launch and
+// its `co` co-launched neighbours share the chip's 256 CUs evenly, so the busiest CU of the launch's share walks
+// rounds = ceil(items * (ngroups + co) / (ngroups * 256)) items, and per K-step of the convolution it stages rounds * step_bytes.
+// Ties go to the fewer bytes staged in total (items * step_bytes: L2 traffic and power), then to `prior`, the tile the
+// work-item thresholds of conv_tile / conv_dma_choice give.  At one pair this means --
+//   * the 256-pixel tile of the same NT wherever it has no more items than the 128-pixel one: 8.9 KB per step instead of 11.1
+//     (Cout 128 / 126 in two chains, the three 64-channel convs of the flow chain), 12.9 instead of 19.1 (NT = 2);
+//   * <2,3,3,1> for Cout 192: 96 items of 12.9 KB, nothing padded, instead of 128 items of 19.1 KB a quarter of whose weight rows
+//     are zero padding -- it beats the two rounds of <1,3,3,1> (192 items, 2 x 8.9 KB) wherever its items fit the share in one;
+// and at batch it keeps <2,3,3,1> (per output its 12.9 KB / 64 channels stay below 8.9 KB / 32).
+// A one-group launch that has the chip to itself (co_groups 0) keeps `prior`: every measurement behind the model was
+// taken with two chains or several groups sharing the chip; the encoders' and the last iteration's launches stay as they were.
+// 1x5 / 5x1 keep conv_dma_choice's rules: the same arithmetic gives the 8-row tile of NT = 1 only -7 % (1x5: 11.2
+// against 12.0 KB) and -6 % (5x1: 13.6 against 14.4 KB) there, too little to tell from noise in the forward.
+// PRIORFLOW_DMA_TALL=0 (A/B knob, read once per process): `prior`, and the tile / roles report that went with it, everywhere.
+static bool dma_tall_rules() {
+    static const bool on = [] { const char* e = getenv("PRIORFLOW_DMA_TALL"); return !e || atoi(e) != 0; }();
+    return on;
+}
+static int conv_dma_tile_3x3(const ConvGeom& g, int ngroups, int co, int max_cout, int prior) {
+    constexpr long CUS = 256;
+    const long chip = ngroups + co;
+    if (chip < 2) return prior;
+    int best = -1;
+    long best_crit = 0, best_total = 0;
+    for (const int cand : {prior, 1 * 4 + 1, 2 * 4 + 1, 1 * 4 + 2, 2 * 4 + 2}) {        // prior first: it wins every tie
+        if (best >= 0 && (cand >> 2) == 2 && max_cout <= 32 * (cand & 3)) continue;       // NT = 2 on one 32 * WN channel block: padding only
+        const DmaTileCost c = dma_tile_cost(g, ngroups, max_cout, cand >> 2, cand & 3);
+        const long rounds = (c.items * chip + ngroups * CUS - 1) / (ngroups * CUS);
+        const long crit = rounds * c.step_bytes, total = c.items * c.step_bytes;
+        if (best < 0 || crit < best_crit || (crit == best_crit && total < best_total)) { best = cand; best_crit = crit; best_total = total; }
+    }
+    return best;
+}
+
 // Pre-split operands (pf_conv_desc.in0_split): which tile the all-DMA kernel takes -- 0: not applicable (fp32 operands,
-// a shape / option it does not implement), else the pf_conv2d_roles code (1: 128-px tile, 2: 256 px x 64 channels).
+// a shape / option it does not implement), else the pf_conv2d_roles code (1: 128-px tile, 2: 256 px x 64 channels; a 3x3
+// launch on tile 3 / 4 then goes through conv_dma_tile_3x3, which may move it to another tile of the same kernel).
 // (The engine's PRIORFLOW_PRESPLIT=0 is the A/B against the register-staged kernels: it hands over fp32 operands.)
 // PF_PREC_F16 exists on this kernel only: a launch it does not take is an error for the caller (conv_plan), never a fallback.
 static int conv_dma_choice(const ConvGroups& grp, int ngroups, const ConvGeom& g, int max_cout, int tile_id) {
@@ -166,8 +219,18 @@ static int conv_plan(const pf_conv_desc* descs, int ngroups, int B, int H8, int 
     if (dma) {                              // pre-split operands: the all-DMA kernel, which reads its zero padding from memory
         for (int i = 0; i < ngroups; ++i)
             if (!descs[i].zeros || descs[i].zeros_bytes < 128 * (descs[i].lds0 > descs[i].lds1 ? descs[i].lds0 : descs[i].lds1)) return PF_ERR_BAD_ARG;
-        p.roles = 16 + dma;
-        p.launch = dma == 2 ? pf_conv_dma_launch<2, 1> : p.tile == 4 ? pf_conv_dma_launch<2, 2> : pf_conv_dma_launch<1, 2>;
+        int nt = (dma == 2 || p.tile == 4) ? 2 : 1, wn = dma == 2 ? 1 : 2;
+        if (g.kh == 3 && (p.tile == 3 || p.tile == 4) && dma_tall_rules()) {
+            // tiles 5 and 8 are <2,3,3,1> by conv_tile's own rules (big maps) and stay.  Here the reported tile follows the
+            // kernel: 3 / 4 = NT 1 / 2, roles 16 + 1 / 16 + 2 = the 128- / 256-pixel tile.  (Without this rule, and for the
+            // 1x5 / 5x1 launches still, the report has tile 3 with 16 + 2 where <2,.,.,1> runs on a map with wgs128 < 256 <= wgs256.)
+            const int t = conv_dma_tile_3x3(g, ngroups, descs[0].co_groups, p.max_cout, nt * 4 + wn);
+            nt = t >> 2; wn = t & 3;
+            p.tile = nt == 1 ? 3 : 4;
+        }
+        p.roles = 16 + (wn == 1 ? 2 : 1);
+        p.launch = wn == 1 ? (nt == 2 ? pf_conv_dma_launch<2, 1> : pf_conv_dma_launch<1, 1>)
+                           : (nt == 2 ? pf_conv_dma_launch<2, 2> : pf_conv_dma_launch<1, 2>);
         return PF_OK;
     }
     for (int i = 0; i < ngroups; ++i) {

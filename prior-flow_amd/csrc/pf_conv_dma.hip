@@ -515,11 +515,11 @@ int launch_conv_dma_t(const ConvGroups& grp, int ngroups, const ConvGeom& g, int
 
 }  // namespace
 
-// One translation unit per kernel shape (PF_DMA_PART = 0..6, 8, 9, compiled in parallel by __graft_entry__.build_hip: an
+// One translation unit per kernel shape (PF_DMA_PART = 0..6, 8..10, compiled in parallel by __graft_entry__.build_hip: an
 // unrolled K-step body takes about a minute per instantiation) plus the family launchers (PF_DMA_PART = 7).  A unit holds both
 // operand forms of its shape (split twins and f16 maps).
 #ifndef PF_DMA_PART
-#error "compile pf_conv_dma.hip with -DPF_DMA_PART=0..9"
+#error "compile pf_conv_dma.hip with -DPF_DMA_PART=0..10"
 #endif
 template <int NT, int KH, int KW, int WN>
 int pf_conv_dma_shape_launch(const pfconv::ConvPlan& p, hipStream_t stream);
@@ -549,16 +549,21 @@ PF_DMA_SHAPE(1, 5, 1, 2)
 PF_DMA_SHAPE(2, 1, 5, 1)
 #elif PF_DMA_PART == 9
 PF_DMA_SHAPE(2, 5, 1, 1)
+#elif PF_DMA_PART == 10
+PF_DMA_SHAPE(1, 3, 3, 1)
 #else
 template <int NT, int WN>
 int pf_conv_dma_launch(const pfconv::ConvPlan& p, hipStream_t stream) {
     const int kh = p.g.kh, kw = p.g.kw;
     if (kh == 3 && kw == 3) return pf_conv_dma_shape_launch<NT, 3, 3, WN>(p, stream);
-    if (kh == 1 && kw == 5) return pf_conv_dma_shape_launch<NT, 1, 5, WN>(p, stream);
-    if (kh == 5 && kw == 1) return pf_conv_dma_shape_launch<NT, 5, 1, WN>(p, stream);
+    if constexpr (NT == 2 || WN == 2) {     // (the 256 px x 32 channel tile is built for 3x3 only)
+        if (kh == 1 && kw == 5) return pf_conv_dma_shape_launch<NT, 1, 5, WN>(p, stream);
+        if (kh == 5 && kw == 1) return pf_conv_dma_shape_launch<NT, 5, 1, WN>(p, stream);
+    }
     return PF_ERR_BAD_SHAPE;                // (no such instantiation: conv_plan names none)
 }
 template int pf_conv_dma_launch<2, 1>(const pfconv::ConvPlan&, hipStream_t);      // 256 px x 64 channels (roles 16 + 2)
+template int pf_conv_dma_launch<1, 1>(const pfconv::ConvPlan&, hipStream_t);      // 256 px x 32 channels (tile 3, roles 16 + 2): 3x3 only
 template int pf_conv_dma_launch<2, 2>(const pfconv::ConvPlan&, hipStream_t);      // 128 px x 128 channels (tile 4, roles 16 + 1)
 template int pf_conv_dma_launch<1, 2>(const pfconv::ConvPlan&, hipStream_t);      // 128 px x 64 channels (tiles 3, 8, roles 16 + 1)
 #endif

@@ -57,7 +57,10 @@ def main():
             for a, b in zip(starts[1:-2], starts[2:-1]):
                 seq = mine[a:b]
                 names = tuple(k[3] for k in seq)
-                chain = ("B" if any("<2, 3, 3, 2>" in n for n in names) else "A") if kind == "pf_lookup" else \
+                # branch B's convc2 has 192 output channels: the 128 px x 128 channel tile, or (with the byte rule of DESIGN.md
+                # section 6) a second 256 px x 64 channel launch beside the FlowHead stem's
+                is_b = any("<2, 3, 3, 2," in n for n in names) or sum("<2, 3, 3, 1," in n for n in names) >= 2
+                chain = ("B" if is_b else "A") if kind == "pf_lookup" else \
                         ("flow" if kind.startswith("pf_motion") else "conf")
                 t_lo, t_hi = mine[a - 1][1] if a else seq[0][0], seq[-1][1]
                 others = [k for k in f if k[2] != q and t_lo - 400_000 < k[1] < t_hi]
