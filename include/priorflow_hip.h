@@ -90,6 +90,47 @@ int pf_forward_interpolate(const float* flow, float* out, void* scratch, long sc
 int pf_fb_check(const float* flow_fw, const float* flow_bw, unsigned char* occ_fw, unsigned char* occ_bw, float* res_fw,
                 float* res_bw, int B, int H, int W, int metric, float alpha, float beta, void* stream);
 
+/* Chained ERP flows: long-range flow and point tracks.  One statement, for a point p = (px, py) in pixels
+ * with px UNWRAPPED (any real number: longitude winds), a flow g [2,H,W] and optionally a mask occ_g [H,W] of bytes (any
+ * non-zero byte counts as 1):
+ *   g^(p) = g sampled at p with the model's cyclic sampler exactly as pf_fb_check samples: x wrapped with the Python modulo,
+ *     y clamped, the bilinear weights from the unclamped fraction, the u component of the three non-anchor taps first brought
+ *     to within W/2 of the anchor tap, v blended plainly;
+ *   m(p) = sum w_i occ_i over the same four taps and weights (0 when occ_g is NULL);
+ *   p' = p + g^(p).  u is NOT clipped to +-W/2: accumulated displacement keeps its winding, only the sampler wraps.
+ *   State is one byte per point and sticky: state' = state | new bits,
+ *     PF_TRK_OCCLUDED   m(p) >= 0.5;
+ *     PF_TRK_POLE       py < -0.5 or py > H - 0.5: the point has left the map through a pole (the sampler still clamps);
+ *     PF_TRK_NONFINITE  the position or a sampled value is not finite; the displacement added is then 0.
+ *   A point with state != 0 is still advanced (dead reckoning); callers mask by state.
+ *
+ * pf_flow_compose, the dense form: out(x) = f(x) + g^(x + f(x)) on the pixel grid, state_out(x) = state_f(x) | new bits, for
+ * njobs = 1..PF_COMPOSE_MAX jobs of one geometry in ONE launch (jobs: host memory, copied into the kernel arguments).  f, g,
+ * out: NCHW [B,2,H,W]; state_f (NULL: read as 0), occ_g (NULL: no mask), state_out (NULL: not written): [B,H,W] bytes.  out may
+ * be f and state_out may be state_f (each pixel is read before it is written).  The jobs of a launch run unordered.
+ * PF_ERR_BAD_ARG: njobs outside 1..PF_COMPOSE_MAX, a NULL jobs / f / g / out, out == g, state_out == occ_g, or an output of one
+ * job that is an operand or output of another.  PF_ERR_BAD_SHAPE: B, H or W < 1, or H * W >= 2^30.  Every refusal answers before
+ * anything is launched.  No scratch memory, no atomics, capturable.
+ *
+ * pf_track_points, the sparse form, in place: pos [B,N,2] fp32 (x, y) with x unwrapped, state [B,N] bytes, flow [B,2,H,W], occ
+ * [B,H,W] bytes or NULL:  pos <- pos + g^(pos), state <- state | new bits.  PF_ERR_BAD_ARG: a NULL pos / state / flow.
+ * PF_ERR_BAD_SHAPE: B, N, H or W < 1, or H * W >= 2^30.
+ * pf_track_grid writes the pixel centres (x, y) of an H x W map as pos [B,H*W,2]: one step of a tracker started there equals
+ * the grid plus pf_flow_compose of a zero flow, bit for bit. */
+#define PF_TRK_OCCLUDED 1
+#define PF_TRK_POLE 2
+#define PF_TRK_NONFINITE 4
+#define PF_COMPOSE_MAX 4
+typedef struct pf_compose_job {
+    const float* f; const unsigned char* state_f;
+    const float* g; const unsigned char* occ_g;
+    float* out; unsigned char* state_out;
+} pf_compose_job;
+int pf_flow_compose(const pf_compose_job* jobs, int njobs, int B, int H, int W, void* stream);
+int pf_track_points(float* pos, unsigned char* state, const float* flow, const unsigned char* occ, int B, int N, int H, int W,
+                    void* stream);
+int pf_track_grid(float* pos, int B, int H, int W, void* stream);
+
 /* Order statistic on the device: out[b] = np.sort(x[b])[k] for each image of x [B, n] (fp32, NON-NEGATIVE values: a length),
  * 0 <= k < n, bit for bit, equal values included; no host read, no allocation, capturable.  A radix select over the bit pattern
  * (11 + 11 + 10 bits; LDS histograms, one integer atomic per non-empty bin and workgroup, so the result does not depend on the

@@ -42,6 +42,11 @@ class PackJob(C.Structure):
                 ("cout_pad", _i), ("cin_pad", _i)]
 
 
+class ComposeJob(C.Structure):
+    """Mirror of ``pf_compose_job`` (include/priorflow_hip.h)."""
+    _fields_ = [("f", _fp), ("state_f", _fp), ("g", _fp), ("occ_g", _fp), ("out", _fp), ("state_out", _fp)]
+
+
 class ConvDesc(C.Structure):
     """Mirror of ``pf_conv_desc`` (include/priorflow_hip.h)."""
     _fields_ = [
@@ -88,6 +93,9 @@ _SIGNATURES = {
     "pf_prepare_frame": [_fp, _fp, _fp, _i, _i, _i, _fp],
     "pf_forward_interpolate": [_fp, _fp, _fp, C.c_long, _i, _i, _i, _i, _fp],
     "pf_fb_check": [_fp] * 6 + [_i, _i, _i, _i, C.c_float, C.c_float, _fp],
+    "pf_flow_compose": [C.POINTER(ComposeJob), _i, _i, _i, _i, _fp],
+    "pf_track_points": [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp],
+    "pf_track_grid": [_fp, _i, _i, _i, _fp],
     "pf_flow_prep": [_fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _i, _fp],
     "pf_flo_rotate": [_fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _i, _fp],
     "pf_corr_pyramid": [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp],
@@ -935,6 +943,59 @@ class PfLib:
         self._rc(self._dll.pf_fb_check(_ptr(flow_fw), _ptr(flow_bw), _ptr(occ_fw), _ptr(occ_bw), _ptr(res_fw), _ptr(res_bw),
                                        B, H, W, self.FB_METRICS[metric], float(alpha), float(beta), self._stream(flow_fw)),
                  "pf_fb_check")
+
+    # ---- chained flows and point tracks --------------------------------
+    TRK_OCCLUDED, TRK_POLE, TRK_NONFINITE = 1, 2, 4     # PF_TRK_*
+    COMPOSE_MAX = 4                                     # PF_COMPOSE_MAX
+
+    def _chk_mask(self, t, shape, what):
+        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
+                              or (self.require_cuda and not t.is_cuda)):
+            raise PfError(f"{what}: expected a contiguous uint8 {tuple(shape)} device tensor")
+
+    def flow_compose(self, jobs):
+        """pf_flow_compose: jobs = 1..4 tuples (f, state_f, g, occ_g, out, state_out) of one geometry, one launch.  f, g, out:
+        fp32 [B,2,H,W]; state_f, occ_g, state_out: uint8 [B,H,W] or None.  out(x) = f(x) + g^(x + f(x)); out may be f."""
+        jobs = list(jobs)
+        if not 1 <= len(jobs) <= self.COMPOSE_MAX:
+            raise PfError(f"flow_compose: {len(jobs)} jobs, expected 1..{self.COMPOSE_MAX}")
+        f0 = jobs[0][0]
+        if f0.dim() != 4 or f0.shape[1] != 2:
+            raise PfError(f"flow_compose: f {tuple(f0.shape)}, expected [B,2,H,W]")
+        B, _, H, W = f0.shape
+        arr = (ComposeJob * len(jobs))()
+        for q, (f, state_f, g, occ_g, out, state_out) in zip(arr, jobs):
+            self._chk(f, g, out)
+            if any(t.shape != f0.shape or t.device != f0.device for t in (f, g, out)):
+                raise PfError("flow_compose: f, g and out of every job must be [B,2,H,W] tensors of one shape and device")
+            for m in (state_f, occ_g, state_out):
+                self._chk_mask(m, (B, H, W), "flow_compose: a state / mask")
+            q.f, q.state_f, q.g, q.occ_g, q.out, q.state_out = (None if t is None else t.data_ptr()
+                                                                for t in (f, state_f, g, occ_g, out, state_out))
+        self._rc(self._dll.pf_flow_compose(arr, len(jobs), B, H, W, self._stream(f0)), "pf_flow_compose")
+
+    def track_points(self, pos, state, flow, occ=None):
+        """pf_track_points, in place: pos fp32 [B,N,2] (x unwrapped, y), state uint8 [B,N], flow [B,2,H,W], occ uint8 [B,H,W]."""
+        self._chk(pos, flow)
+        if pos.dim() != 3 or pos.shape[2] != 2 or flow.dim() != 4 or flow.shape[1] != 2 or flow.shape[0] != pos.shape[0]:
+            raise PfError(f"track_points: pos {tuple(pos.shape)} / flow {tuple(flow.shape)}, expected [B,N,2] and [B,2,H,W]")
+        B, N, _ = pos.shape
+        H, W = flow.shape[2:]
+        self._chk_mask(state, (B, N), "track_points: state")
+        self._chk_mask(occ, (B, H, W), "track_points: occ")
+        if state is None:
+            raise PfError("track_points: state is required")
+        self._rc(self._dll.pf_track_points(_ptr(pos), _ptr(state), _ptr(flow), _ptr(occ), B, N, H, W, self._stream(pos)),
+                 "pf_track_points")
+        return pos, state
+
+    def track_grid(self, pos, H: int, W: int):
+        """pf_track_grid: the pixel centres (x, y) of an H x W map into pos fp32 [B,H*W,2]."""
+        self._chk(pos)
+        if pos.dim() != 3 or tuple(pos.shape[1:]) != (H * W, 2):
+            raise PfError(f"track_grid: pos {tuple(pos.shape)}, expected [B,{H * W},2]")
+        self._rc(self._dll.pf_track_grid(_ptr(pos), pos.shape[0], H, W, self._stream(pos)), "pf_track_grid")
+        return pos
 
     def region_sums(self, epe, sd, weight, bits, nregions, partials):
         """epe, sd: [B,H,W]; weight: [H*W] or None; bits: uint8 [H*W]; partials: float64 [B,nblk,nregions,3]."""

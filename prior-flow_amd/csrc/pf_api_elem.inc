@@ -436,6 +436,50 @@ extern "C" int pf_fb_check(const float* flow_fw, const float* flow_bw, unsigned 
     return PF_FB_CHECK_LAUNCH(a, 2L * B * H * W, stream);
 }
 
+// flow composition: the device build defines PF_FLOW_COMPOSE_LAUNCH (four pixels per thread where alignment allows)
+#ifndef PF_FLOW_COMPOSE_LAUNCH
+#define PF_FLOW_COMPOSE_LAUNCH(a, total, stream) PF_LAUNCH(flow_compose, a, total, stream)
+#endif
+extern "C" int pf_flow_compose(const pf_compose_job* jobs, int njobs, int B, int H, int W, void* stream) {
+    PF_REQUIRE(jobs && njobs >= 1 && njobs <= PF_COMPOSE_MAX);
+    PF_REQUIRE_SHAPE(B > 0 && H > 0 && W > 0 && (long)H * W < (1L << 30));
+    PfComposeArgs a;
+    for (int i = 0; i < PF_COMPOSE_MAX; ++i) {
+        const pf_compose_job& j = jobs[i < njobs ? i : 0];
+        PF_REQUIRE(j.f && j.g && j.out && j.out != j.g && (!j.state_out || j.state_out != j.occ_g));
+        PF_REQUIRE((const void*)j.out != j.state_f && (const void*)j.out != j.occ_g && (void*)j.out != j.state_out &&
+                   (const void*)j.state_out != j.f && (const void*)j.state_out != j.g);
+        PfComposeJob& q = a.job[i];
+        q.f = j.f; q.state_f = j.state_f; q.g = j.g; q.occ_g = j.occ_g; q.out = j.out; q.state_out = j.state_out;
+    }
+    for (int i = 0; i < njobs; ++i)             // the jobs run unordered: no output of one may be touched by another
+        for (int k = 0; k < njobs; ++k) {
+            if (k == i) continue;
+            const PfComposeJob& w = a.job[i]; const PfComposeJob& o = a.job[k];
+            const void* outs[2] = {w.out, w.state_out};
+            const void* theirs[6] = {o.f, o.state_f, o.g, o.occ_g, o.out, o.state_out};
+            for (const void* p : outs)
+                for (const void* t : theirs) PF_REQUIRE(!p || p != t);
+        }
+    a.njobs = njobs; a.B = B; a.H = H; a.W = W;
+    return PF_FLOW_COMPOSE_LAUNCH(a, (long)njobs * B * H * W, stream);
+}
+
+extern "C" int pf_track_points(float* pos, unsigned char* state, const float* flow, const unsigned char* occ, int B, int N,
+                               int H, int W, void* stream) {
+    PF_REQUIRE(pos && state && flow && (const void*)pos != flow && (const void*)state != occ);
+    PF_REQUIRE_SHAPE(B > 0 && N > 0 && H > 0 && W > 0 && (long)H * W < (1L << 30));
+    PfTrackArgs a; a.pos = pos; a.state = state; a.flow = flow; a.occ = occ; a.B = B; a.N = N; a.H = H; a.W = W;
+    return PF_LAUNCH(track_points, a, (long)B * N, stream);
+}
+
+extern "C" int pf_track_grid(float* pos, int B, int H, int W, void* stream) {
+    PF_REQUIRE(pos);
+    PF_REQUIRE_SHAPE(B > 0 && H > 0 && W > 0 && (long)H * W < (1L << 30));
+    PfTrackArgs a; a.pos = pos; a.state = nullptr; a.flow = nullptr; a.occ = nullptr; a.B = B; a.N = H * W; a.H = H; a.W = W;
+    return PF_LAUNCH(track_grid, a, (long)B * H * W, stream);
+}
+
 extern "C" int pf_region_sums(const float* epe, const float* sd, const float* weight, const unsigned char* bits,
                               int nregions, double* partials, int nblk, int B, int N, void* stream) {
     PF_REQUIRE(epe && sd && bits && partials);

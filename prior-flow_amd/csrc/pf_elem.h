@@ -1387,6 +1387,92 @@ PF_HD void pf_fb_check_elem(long idx, const PfFbCheckArgs& a) {   // idx over 2*
     res[n] = o.ru; res[N + n] = o.rv;
 }
 
+// ----------------------------------------------------------------------------------------------
+// Chained ERP flows: long-range flow and point tracks (include/priorflow_hip.h: pf_flow_compose, pf_track_points;
+// DESIGN.md section 17).  pf_trk_point is the whole statement for one point and one flow; the dense element form, the
+// device's 4-pixels-per-thread kernel (pf_elem_kernels.hip) and the sparse form call it, so all give the same bits.
+// ----------------------------------------------------------------------------------------------
+struct PfTrkOut { float gu, gv; unsigned char bits; };     // the displacement to add (0 when not finite), the NEW state bits
+// g0: the u plane of one image's flow [2,H,W]; occ: that image's mask [H,W] or null; p = (px, py), px unwrapped
+PF_HD PfTrkOut pf_trk_point(const float* g0, const unsigned char* occ, int H, int W, float px, float py) {
+    const float Wf = (float)W;
+    const float* g1 = g0 + (long)H * W;
+    const PfWrapTaps t = pf_wraptaps(px, py, H, W);                       // indices always inside the map (NaN / huge included)
+    const float a0 = g0[t.ia];
+    PfTrkOut o;
+    o.gu = pf_wrapmix(t, a0, pf_unwrap_m(a0, g0[t.ib], Wf), pf_unwrap_m(a0, g0[t.ic], Wf), pf_unwrap_m(a0, g0[t.id], Wf));
+    o.gv = pf_wrapmix(t, g1[t.ia], g1[t.ib], g1[t.ic], g1[t.id]);
+    o.bits = 0;
+    if (occ) {
+        const float m = pf_wrapmix(t, occ[t.ia] ? 1.f : 0.f, occ[t.ib] ? 1.f : 0.f, occ[t.ic] ? 1.f : 0.f, occ[t.id] ? 1.f : 0.f);
+        if (m >= 0.5f) o.bits |= 1;                                       // PF_TRK_OCCLUDED (a NaN weight decides nothing)
+    }
+    if (py < -0.5f || py > (float)H - 0.5f) o.bits |= 2;                  // PF_TRK_POLE: flagged, still sampled on the clamped row
+    if (!(pf_finite(px) && pf_finite(py) && pf_finite(o.gu) && pf_finite(o.gv))) {
+        o.gu = 0.f; o.gv = 0.f; o.bits |= 4;                              // PF_TRK_NONFINITE
+    }
+    return o;
+}
+struct PfComposeJob {
+    const float* f; const unsigned char* state_f;       // [B,2,H,W], [B,H,W] or null (read as 0)
+    const float* g; const unsigned char* occ_g;         // [B,2,H,W], [B,H,W] or null
+    float* out; unsigned char* state_out;               // [B,2,H,W] (may be f), [B,H,W] or null (may be state_f)
+};
+#define PF_COMPOSE_MAX 4
+struct PfComposeArgs { PfComposeJob job[PF_COMPOSE_MAX]; int njobs, B, H, W; };
+// job j, field by field from values loaded with constant indices: a kernel argument indexed by a run-time value (or chosen by
+// address) would be copied to scratch memory
+template <class T> PF_HD T pf_pick4(int j, T v0, T v1, T v2, T v3) { return j == 0 ? v0 : (j == 1 ? v1 : (j == 2 ? v2 : v3)); }
+#define PF_COMPOSE_FIELD(m) pf_pick4(j, a.job[0].m, a.job[1].m, a.job[2].m, a.job[3].m)
+PF_HD PfComposeJob pf_compose_pick(const PfComposeArgs& a, int j) {
+    PfComposeJob q;
+    q.f = PF_COMPOSE_FIELD(f); q.state_f = PF_COMPOSE_FIELD(state_f); q.g = PF_COMPOSE_FIELD(g);
+    q.occ_g = PF_COMPOSE_FIELD(occ_g); q.out = PF_COMPOSE_FIELD(out); q.state_out = PF_COMPOSE_FIELD(state_out);
+    return q;
+}
+#undef PF_COMPOSE_FIELD
+struct PfComposeOut { float u, v; unsigned char state; };
+// pixel (x, y) of image b of job q, f = (fu, fv) and the state byte sf there: out = f + g^(p), p = (x, y) + f
+PF_HD PfComposeOut pf_compose_pixel(const PfComposeJob& q, int H, int W, long b, int y, int x, float fu, float fv, unsigned char sf) {
+    const long N = (long)H * W;
+    const PfTrkOut t = pf_trk_point(q.g + b * 2 * N, q.occ_g ? q.occ_g + b * N : nullptr, H, W, (float)x + fu, (float)y + fv);
+    PfComposeOut o;
+    o.u = fu + t.gu; o.v = fv + t.gv; o.state = (unsigned char)(sf | t.bits);
+    return o;
+}
+PF_HD void pf_flow_compose_elem(long idx, const PfComposeArgs& a) {       // idx over njobs*B*H*W: job, image, pixel
+    const long N = (long)a.H * a.W, BN = (long)a.B * N;
+    const PfComposeJob q = pf_compose_pick(a, (int)(idx / BN));
+    const long r = idx % BN, b = r / N, n = r % N;
+    const int y = (int)n / a.W;                  // H * W < 2^30 (checked by the entry point): a 32-bit division
+    const float* f = q.f + b * 2 * N;
+    const PfComposeOut o = pf_compose_pixel(q, a.H, a.W, b, y, (int)n - y * a.W, f[n], f[N + n], q.state_f ? q.state_f[r] : 0);
+    float* out = q.out + b * 2 * N;              // every read of this pixel is done: out may be f, state_out may be state_f
+    out[n] = o.u; out[N + n] = o.v;
+    if (q.state_out) q.state_out[r] = o.state;
+}
+PF_HD void pf_store2(float* p, float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef float pf_f2u __attribute__((ext_vector_type(2), aligned(4)));     // dword-aligned 8-byte store
+    pf_f2u v; v.x = a; v.y = b;
+    *reinterpret_cast<pf_f2u*>(p) = v;
+#else
+    p[0] = a; p[1] = b;
+#endif
+}
+struct PfTrackArgs { float* pos; unsigned char* state; const float* flow; const unsigned char* occ; int B, N, H, W; };
+PF_HD void pf_track_points_elem(long idx, const PfTrackArgs& a) {         // idx over B*N: pos <- pos + g^(pos), in place
+    const long b = idx / a.N, hw = (long)a.H * a.W;
+    const PfPair p = pf_load2(a.pos + 2 * idx);
+    const PfTrkOut t = pf_trk_point(a.flow + b * 2 * hw, a.occ ? a.occ + b * hw : nullptr, a.H, a.W, p.a, p.b);
+    pf_store2(a.pos + 2 * idx, p.a + t.gu, p.b + t.gv);
+    a.state[idx] = (unsigned char)(a.state[idx] | t.bits);
+}
+PF_HD void pf_track_grid_elem(long idx, const PfTrackArgs& a) {           // idx over B*H*W: the pixel centres (x, y)
+    const int n = (int)(idx % ((long)a.H * a.W)), y = n / a.W;
+    pf_store2(a.pos + 2 * idx, (float)(n - y * a.W), (float)y);
+}
+
 // Region sums (evaluate.py:246-275): pixel n belongs to region r when bit r of bits[n] is set.
 // partials[((b*nblk + k)*R + r)*3 + {0,1,2}] = sum epe, sum sd, sum sd*weight over block k's pixels.
 struct PfRegionSumArgs {

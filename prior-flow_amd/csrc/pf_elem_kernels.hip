@@ -1274,6 +1274,47 @@ int launch_fb_check(const PfFbCheckArgs& a, long total, void* stream) {
     return (int)hipGetLastError();
 }
 
+// Flow composition, four consecutive pixels of a row per thread (W % 4 == 0, 16-byte aligned maps): f is
+// read and out written as 16-byte vectors, the four state bytes as one dword, the jobs of a launch along blockIdx.y (so a
+// job's pointers stay in scalar registers).  The 4-tap gathers of g and occ_g stay scalar loads (their columns wrap at the
+// seam).  A thread reads its four pixels before it writes them: out may be f.  pf_compose_pixel is the element form's statement.
+__global__ void __launch_bounds__(kBlock) pf_flow_compose_vec4(const PfComposeArgs a, const long total4) {
+    const PfComposeJob q = pf_compose_pick(a, (int)blockIdx.y);
+    const long N = (long)a.H * a.W;
+    long i = (long)blockIdx.x * kBlock + threadIdx.x;
+    const long stride = (long)gridDim.x * kBlock;
+    for (; i < total4; i += stride) {                                 // i over B*H*W/4 of one job
+        const long r = i * 4, b = r / N, n = r % N;
+        const int y = (int)n / a.W, x = (int)n - y * a.W;            // H * W < 2^30: a 32-bit division
+        const float* f = q.f + b * 2 * N + n;
+        const float4 fu = *reinterpret_cast<const float4*>(f), fv = *reinterpret_cast<const float4*>(f + N);
+        const unsigned sf = q.state_f ? *reinterpret_cast<const unsigned*>(q.state_f + r) : 0u;
+        const PfComposeOut o0 = pf_compose_pixel(q, a.H, a.W, b, y, x, fu.x, fv.x, (unsigned char)(sf & 255u));
+        const PfComposeOut o1 = pf_compose_pixel(q, a.H, a.W, b, y, x + 1, fu.y, fv.y, (unsigned char)((sf >> 8) & 255u));
+        const PfComposeOut o2 = pf_compose_pixel(q, a.H, a.W, b, y, x + 2, fu.z, fv.z, (unsigned char)((sf >> 16) & 255u));
+        const PfComposeOut o3 = pf_compose_pixel(q, a.H, a.W, b, y, x + 3, fu.w, fv.w, (unsigned char)(sf >> 24));
+        float* out = q.out + b * 2 * N + n;
+        *reinterpret_cast<float4*>(out) = make_float4(o0.u, o1.u, o2.u, o3.u);
+        *reinterpret_cast<float4*>(out + N) = make_float4(o0.v, o1.v, o2.v, o3.v);
+        if (q.state_out)
+            *reinterpret_cast<unsigned*>(q.state_out + r) =
+                (unsigned)o0.state | ((unsigned)o1.state << 8) | ((unsigned)o2.state << 16) | ((unsigned)o3.state << 24);
+    }
+}
+int launch_flow_compose(const PfComposeArgs& a, long total, void* stream) {
+    bool vec = a.W % 4 == 0;
+    for (int j = 0; j < a.njobs; ++j) {
+        const PfComposeJob& q = a.job[j];
+        vec = vec && ((uintptr_t)q.f | (uintptr_t)q.out) % 16 == 0 && ((uintptr_t)q.state_f | (uintptr_t)q.state_out) % 4 == 0;
+    }
+    if (!vec) return pf_launch_elem<PfComposeArgs, pf_flow_compose_elem>(a, total, stream);
+    const long n4 = total / a.njobs / 4;
+    long blocks = (n4 + kBlock - 1) / kBlock;
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+    hipLaunchKernelGGL(pf_flow_compose_vec4, dim3((unsigned)blocks, (unsigned)a.njobs), dim3(kBlock), 0, (hipStream_t)stream, a, n4);
+    return (int)hipGetLastError();
+}
+
 // ---- flow rendering -------------------------------------------------------------------------------------
 // The choice after pass p - 1 by one 256-thread workgroup: every thread sums a run of bins, a Hillis-Steele scan of the run sums,
 // and the one thread whose run holds the rank walks it.  sel = {new prefix, remaining rank}; pf_os_select_image is the statement.
@@ -1481,6 +1522,7 @@ int launch_masked_mean(const PfMaskedMeanArgs& a, void* stream) {
 #define PF_RENDER_COLOR_LAUNCH(o, r, stream) launch_render_color(o, r, stream)
 #define PF_MASKED_MEAN_LAUNCH(a, stream) launch_masked_mean(a, stream)
 #define PF_FB_CHECK_LAUNCH(a, total, stream) launch_fb_check(a, total, stream)
+#define PF_FLOW_COMPOSE_LAUNCH(a, total, stream) launch_flow_compose(a, total, stream)
 #define PF_LOOKUP_BWD_LAUNCH(a, total, stream) launch_lookup_bwd(a, total, stream)
 #define PF_UPSAMPLE_BWD_LAUNCH(a, total, stream) launch_upsample_bwd(a, total, stream)
 #define PF_COMBINE_LAUNCH(a, total, stream) launch_combine(a, total, stream)
