@@ -257,6 +257,39 @@ int pf_viewport_flow(const float* flow, const float* views_host, int V, float* o
                      float min_forward, void* stream);
 int pf_cubemap_to_erp(const float* faces, float* out, int B, int C, int s, int H, int W, void* stream);
 
+/* Forward softmax splatting (the statement is prior-flow_amd/csrc/pf_splat.h): maps are moved ALONG their
+ * flow and blended, e.g. the frame at time t between two frames from the two flows between them.  Two launches per call:
+ *
+ * pf_splat_accumulate: njobs = 1..PF_SPLAT_MAX jobs of one geometry (jobs: host memory, copied into the kernel arguments).  Job j:
+ *   src [B,C,H,W] fp32 (C = 1..4), flow [B,2,H,W], metric [B,cm,H,W] or NULL (cm = 1: m = |metric|, cm = 2: the Euclidean length
+ *   of the two planes), mask [B,H,W] bytes or NULL (non-zero: the pixel is skipped), tau (how far along the flow), beta in (0, 1].
+ *   Source pixel (x, y): q = (x + tau u, y + tau v) in fp32; w = beta expf(-min(alpha m, zmax)) (beta without a metric or at
+ *   alpha = 0); skipped when masked or when q, m or one of its values is not finite (|q| >= 2^30 counts as not finite); four
+ *   bilinear taps, the columns wrapped with the Python modulo, a row outside [0, H - 1] dropped (not clamped); per target p
+ *     N_c[p] += w b_k clamp(src_c, +-vmax),  D[p] += w b_k,  cov[p] += beta b_k
+ *   as 64-bit INTEGERS: each contribution is llrintf(value * 2^S) with S_D = S_cov = 62 - ceil(log2(njobs H W)) and
+ *   S_N = S_D - ceil(log2(vmax)), so no sum can overflow and the result does not depend on the order of the adds.
+ *   acc: [B][C+2][H][W] int64 (pf_splat_scratch_bytes), all-zero on entry.
+ * pf_splat_resolve: per target pixel hole = cov < cmin (or D <= 0), out_c = N_c / D; a hole takes (1 - fill_t) fill0 + fill_t
+ *   fill1 ([B,C,H,W] maps, both or neither) or 0; hole [B,H,W] bytes; the sums are written back as zeros: acc is all-zero again.
+ *   njobs and vmax must be the accumulate call's (they fix the scales).
+ * PF_ERR_BAD_ARG: a NULL jobs / acc / src / flow / out / hole, njobs outside 1..PF_SPLAT_MAX, C outside 1..4, cm outside {1, 2}
+ * with a metric, tau not finite, beta outside (0, 1], alpha < 0, zmax < 0, vmax outside [1, 65536], cmin <= 0, acc not 8-byte
+ * aligned or aliasing an operand, one fill map without the other, fill_t outside [0, 1], out aliasing a fill map (a source).
+ * PF_ERR_BAD_SHAPE: B, H or W < 1, B > 65535, H * W >= 2^30.  Every refusal answers before anything is launched.  No host read,
+ * no allocation, capturable. */
+#define PF_SPLAT_MAX 4
+typedef struct pf_splat_job {
+    const float* src; const float* flow;
+    const float* metric; const unsigned char* mask;
+    int cm; float tau; float beta;
+} pf_splat_job;
+long pf_splat_scratch_bytes(int B, int C, int H, int W);
+int pf_splat_accumulate(const pf_splat_job* jobs, int njobs, void* acc, int B, int C, int H, int W, float alpha, float zmax,
+                        float vmax, void* stream);
+int pf_splat_resolve(void* acc, float* out, unsigned char* hole, const float* fill0, const float* fill1, float fill_t, float cmin,
+                     int njobs, int B, int C, int H, int W, float vmax, void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

@@ -47,6 +47,11 @@ class ComposeJob(C.Structure):
     _fields_ = [("f", _fp), ("state_f", _fp), ("g", _fp), ("occ_g", _fp), ("out", _fp), ("state_out", _fp)]
 
 
+class SplatJob(C.Structure):
+    """Mirror of ``pf_splat_job`` (include/priorflow_hip.h)."""
+    _fields_ = [("src", _fp), ("flow", _fp), ("metric", _fp), ("mask", _fp), ("cm", _i), ("tau", C.c_float), ("beta", C.c_float)]
+
+
 class ConvDesc(C.Structure):
     """Mirror of ``pf_conv_desc`` (include/priorflow_hip.h)."""
     _fields_ = [
@@ -174,12 +179,17 @@ _SIGNATURES = {
     "pf_viewport_image": [_fp, _fp, C.POINTER(C.c_float), _i, _i, _i, _i, _i, _i, _fp],
     "pf_viewport_flow": [_fp, C.POINTER(C.c_float), _i, _fp, _fp, _i, _i, _i, C.c_float, _fp],
     "pf_cubemap_to_erp": [_fp, _fp, _i, _i, _i, _i, _i, _fp],
+    "pf_splat_scratch_bytes": [_i, _i, _i, _i],
+    "pf_splat_accumulate": [C.POINTER(SplatJob), _i, _fp, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, _fp],
+    "pf_splat_resolve": [_fp, _fp, _fp, _fp, _fp, C.c_float, C.c_float, _i, _i, _i, _i, _i, C.c_float, _fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
-# entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp): a host-only
-# handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+# entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp,
+# pf_emu_splat.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
 _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert",
-                  "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp")
+                  "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp",
+                  "pf_splat_scratch_bytes", "pf_splat_accumulate", "pf_splat_resolve")
+SPLAT_MAX = 4                                       # PF_SPLAT_MAX
 AUG_ROW_WORDS = 32                                  # PF_AUG_ROW_WORDS
 VIEW_MAX, VIEW_WORDS = 16, 12                       # PF_VIEW_MAX, PF_VIEW_WORDS
 VIEW_F32, VIEW_U8 = 0, 1                            # PF_VIEW_F32 / PF_VIEW_U8
@@ -1170,6 +1180,63 @@ class PfLib:
         self._rc(self._dll.pf_cubemap_to_erp(_ptr(faces), _ptr(out), B, Cc, faces.shape[3], H, W, self._stream(faces)),
                  "pf_cubemap_to_erp")
         return out
+
+    # ---- forward softmax splatting -------------------------------------
+    def splat_scratch_bytes(self, B: int, C_: int, H: int, W: int) -> int:
+        self._have("pf_splat_scratch_bytes")
+        r = self._dll.pf_splat_scratch_bytes(B, C_, H, W)
+        self._rc(min(r, 0), "pf_splat_scratch_bytes")
+        return r
+
+    def _chk_splat_acc(self, acc, B, Cc, H, W):
+        self._chk_bytes(acc, "splat: acc", torch.int64)
+        if tuple(acc.shape) != (B, Cc + 2, H, W):
+            raise PfError(f"splat: acc {tuple(acc.shape)}, expected {(B, Cc + 2, H, W)}")
+
+    def splat_accumulate(self, jobs, acc, alpha: float, zmax: float, vmax: float):
+        """pf_splat_accumulate: jobs = 1..4 tuples (src, flow, metric, mask, tau, beta) of one geometry, one launch.  src fp32
+        [B,C,H,W], flow [B,2,H,W], metric [B,1|2,H,W] or None, mask uint8 [B,H,W] or None; acc int64 [B,C+2,H,W] (all-zero)."""
+        self._have("pf_splat_accumulate")
+        jobs = list(jobs)
+        if not 1 <= len(jobs) <= SPLAT_MAX:
+            raise PfError(f"splat_accumulate: {len(jobs)} jobs, expected 1..{SPLAT_MAX}")
+        s0 = jobs[0][0]
+        if s0.dim() != 4:
+            raise PfError(f"splat_accumulate: src {tuple(s0.shape)}, expected [B,C,H,W]")
+        B, Cc, H, W = s0.shape
+        self._chk_splat_acc(acc, B, Cc, H, W)
+        arr = (SplatJob * len(jobs))()
+        for q, (src, flow, metric, mask, tau, beta) in zip(arr, jobs):
+            self._chk(src, flow, metric)
+            if src.shape != s0.shape or tuple(flow.shape) != (B, 2, H, W) or any(
+                    t is not None and t.device != acc.device for t in (src, flow, metric, mask)):
+                raise PfError(f"splat_accumulate: src {tuple(src.shape)} / flow {tuple(flow.shape)} do not fit {tuple(s0.shape)} on {acc.device}")
+            if metric is not None and (metric.dim() != 4 or metric.shape[1] not in (1, 2) or tuple(metric.shape[::2]) != (B, H)
+                                       or metric.shape[3] != W):
+                raise PfError(f"splat_accumulate: metric {tuple(metric.shape)}, expected [B,1,H,W] or [B,2,H,W]")
+            self._chk_mask(mask, (B, H, W), "splat_accumulate: mask")
+            q.src, q.flow, q.metric, q.mask = (None if t is None else t.data_ptr() for t in (src, flow, metric, mask))
+            q.cm, q.tau, q.beta = (0 if metric is None else metric.shape[1]), float(tau), float(beta)
+        self._rc(self._dll.pf_splat_accumulate(arr, len(jobs), _ptr(acc), B, Cc, H, W, float(alpha), float(zmax), float(vmax),
+                                               self._stream(s0)), "pf_splat_accumulate")
+
+    def splat_resolve(self, acc, out, hole, njobs: int, vmax: float, cmin: float, fill0=None, fill1=None, fill_t: float = 0.0):
+        """pf_splat_resolve: out fp32 [B,C,H,W] and hole uint8 [B,H,W] from acc (zeroed again); njobs, vmax: the accumulate
+        call's.  fill0, fill1 [B,C,H,W] (both or neither): a hole takes (1 - fill_t) fill0 + fill_t fill1, else 0."""
+        self._have("pf_splat_resolve")
+        self._chk(out, fill0, fill1)
+        if out.dim() != 4:
+            raise PfError(f"splat_resolve: out {tuple(out.shape)}, expected [B,C,H,W]")
+        B, Cc, H, W = out.shape
+        self._chk_splat_acc(acc, B, Cc, H, W)
+        self._chk_mask(hole, (B, H, W), "splat_resolve: hole")
+        if hole is None or (fill0 is None) != (fill1 is None) or any(f is not None and f.shape != out.shape for f in (fill0, fill1)):
+            raise PfError("splat_resolve: hole is required; fill0 and fill1 go together and have out's shape")
+        if any(t is not None and t.device != acc.device for t in (out, hole, fill0, fill1)):
+            raise PfError("splat_resolve: every tensor must be on acc's device")
+        self._rc(self._dll.pf_splat_resolve(_ptr(acc), _ptr(out), _ptr(hole), _ptr(fill0), _ptr(fill1), float(fill_t), float(cmin),
+                                            int(njobs), B, Cc, H, W, float(vmax), self._stream(out)), "pf_splat_resolve")
+        return out, hole
 
     def masked_mean(self, x, mask, out, scratch):
         """out[b] = mean of x[b] over mask[b] == 0 (mask None: everything); scratch: >= 1024 * B bytes."""
