@@ -290,6 +290,47 @@ int pf_splat_accumulate(const pf_splat_job* jobs, int njobs, void* acc, int B, i
 int pf_splat_resolve(void* acc, float* out, unsigned char* hole, const float* fill0, const float* fill1, float fill_t, float cmin,
                      int njobs, int B, int C, int H, int W, float vmax, void* stream);
 
+/* Camera rotation from 360-degree flow, and stabilisation (the statement is
+ * prior-flow_amd/csrc/pf_egomotion.h).  On the sphere a camera rotation moves every bearing rigidly: with p = s(x, y) and
+ * q = s(x + u, clamp(y + v, -1/2, H - 1/2)) (the ERP convention of the viewports above) the rotation sought has q ~ R p.  A pixel
+ * is left out when its mask byte is non-zero or |u| or |v| is not below 2^30 (not finite included).  Every matrix is nine fp32
+ * values row-major in DEVICE memory, [B,9].
+ *
+ * pf_ego_accumulate: one pass over flow [B,2,H,W] (mask [B,H,W] bytes or NULL): the twelve sums per image S_ab = sum w p_a q_b,
+ *   sum w, sum w r^2 and the number of pixels used, added into sums [B,12] int64 (pf_ego_scratch_bytes; all-zero before the
+ *   first pass).  w = cos phi(y) without weights (weighted = 0), times the Geman-McClure weight 1 / (1 + r^2 / c^2)^2 with
+ *   weighted = 1; r = |q - R p| is the chord under the matrix R of the pass before, c = scale_px 2 pi / W.  The sums are INTEGERS, a
+ *   contribution llrintf(value * 2^S) with S = 62 - ceil(log2(H W)) (S - 2 for sum w r^2): no sum can overflow and the result
+ *   does not depend on the order of the adds or on the grid.  blocks: workgroups per image, 0 = chosen from the CU count.
+ * pf_ego_solve: per image Horn's 4 x 4 matrix of S, its largest eigenvector by cyclic Jacobi in fp64, the quaternion with a
+ *   non-negative scalar part, R its matrix; stats [B,5] = {sum w, rms chord sqrt(sum w r^2 / sum w), used / (H W),
+ *   gap = (lambda_1 - lambda_2) / sum w, valid}.  valid = 0 when sum w = 0 or gap < gap_min; then R = init (NULL: the identity).
+ *   The sums are written back as zeros.  An estimate of k passes is accumulate(weighted = 0, R = init), solve, then k - 1 times
+ *   accumulate(weighted = 1, R = the R just solved), solve.
+ * pf_ego_track: state [B,8] fp64 = two unit quaternions {O, S} ({1,0,0,0, 1,0,0,0} at the start).  O_t = R_t O_{t-1},
+ *   renormalised; S_t = slerp(S_{t-1}, O_t, 1 - smoothing); orient = O_t, corr = O_t S_t^T.  smoothing 1 locks the view to the
+ *   first frame (corr = O_t), 0 leaves the video as it is (corr = I).
+ * pf_erp_rotate: out(x, y) = in sampled at the ERP position of R s(x, y), four taps, columns wrap, rows clamp; PF_VIEW_F32:
+ *   [B,C,H,W] fp32, PF_VIEW_U8: [B,H,W,C] bytes, C = 1..4.
+ * pf_ego_derotate: out(x, y) = (ERP position of R^T q) - (x, y), the first component wrapped into [-W/2, W/2); a left-out pixel
+ *   gives (0, 0) and valid 0 (valid [B,H,W] bytes or NULL).  out may be flow.
+ * PF_ERR_BAD_ARG: a NULL flow / R / sums / stats / state / orient / corr / in / out, sums or state not 8-byte aligned, outputs
+ * aliasing each other or an input (but out == flow of pf_ego_derotate), weighted outside {0, 1}, blocks outside 0..65535,
+ * scale_px not positive and finite, gap_min negative, smoothing outside [0, 1], C outside 1..4, an unknown form.
+ * PF_ERR_BAD_SHAPE: B, H or W < 1, B > 65535, H * W >= 2^30.  Every refusal answers before anything is launched.  One launch
+ * each, no host read, no allocation, capturable. */
+#define PF_EGO_SUMS 12
+#define PF_EGO_STATS 5
+#define PF_EGO_STATE 8
+long pf_ego_scratch_bytes(int B, int H, int W);
+int pf_ego_accumulate(const float* flow, const unsigned char* mask, const float* R, void* sums, int B, int H, int W, int weighted,
+                      float scale_px, int blocks, void* stream);
+int pf_ego_solve(void* sums, const float* init, float* R, float* stats, int B, int H, int W, float gap_min, void* stream);
+int pf_ego_track(const float* R, void* state, float* orient, float* corr, int B, float smoothing, void* stream);
+int pf_erp_rotate(const void* in, void* out, const float* R, int B, int C, int H, int W, int form, void* stream);
+int pf_ego_derotate(const float* flow, const unsigned char* mask, const float* R, float* out, unsigned char* valid, int B, int H, int W,
+                    void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

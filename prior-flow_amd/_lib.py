@@ -182,13 +182,21 @@ _SIGNATURES = {
     "pf_splat_scratch_bytes": [_i, _i, _i, _i],
     "pf_splat_accumulate": [C.POINTER(SplatJob), _i, _fp, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, _fp],
     "pf_splat_resolve": [_fp, _fp, _fp, _fp, _fp, C.c_float, C.c_float, _i, _i, _i, _i, _i, C.c_float, _fp],
+    "pf_ego_scratch_bytes": [_i, _i, _i],
+    "pf_ego_accumulate": [_fp, _fp, _fp, _fp, _i, _i, _i, _i, C.c_float, _i, _fp],
+    "pf_ego_solve": [_fp, _fp, _fp, _fp, _i, _i, _i, C.c_float, _fp],
+    "pf_ego_track": [_fp, _fp, _fp, _fp, _i, C.c_float, _fp],
+    "pf_erp_rotate": [_fp, _fp, _fp, _i, _i, _i, _i, _i, _fp],
+    "pf_ego_derotate": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
 # entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp,
-# pf_emu_splat.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+# pf_emu_splat.cpp, pf_emu_egomotion.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
 _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert",
                   "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp",
-                  "pf_splat_scratch_bytes", "pf_splat_accumulate", "pf_splat_resolve")
+                  "pf_splat_scratch_bytes", "pf_splat_accumulate", "pf_splat_resolve",
+                  "pf_ego_scratch_bytes", "pf_ego_accumulate", "pf_ego_solve", "pf_ego_track", "pf_erp_rotate", "pf_ego_derotate")
+EGO_SUMS, EGO_STATS, EGO_STATE = 12, 5, 8           # PF_EGO_SUMS, PF_EGO_STATS, PF_EGO_STATE
 SPLAT_MAX = 4                                       # PF_SPLAT_MAX
 AUG_ROW_WORDS = 32                                  # PF_AUG_ROW_WORDS
 VIEW_MAX, VIEW_WORDS = 16, 12                       # PF_VIEW_MAX, PF_VIEW_WORDS
@@ -1237,6 +1245,100 @@ class PfLib:
         self._rc(self._dll.pf_splat_resolve(_ptr(acc), _ptr(out), _ptr(hole), _ptr(fill0), _ptr(fill1), float(fill_t), float(cmin),
                                             int(njobs), B, Cc, H, W, float(vmax), self._stream(out)), "pf_splat_resolve")
         return out, hole
+
+    # ---- camera rotation from 360-degree flow --------------------------
+    def ego_scratch_bytes(self, B: int, H: int, W: int) -> int:
+        self._have("pf_ego_scratch_bytes")
+        r = self._dll.pf_ego_scratch_bytes(B, H, W)
+        self._rc(min(r, 0), "pf_ego_scratch_bytes")
+        return r
+
+    def _chk_ego_mats(self, B, what, **mats):
+        """Rotation matrices [B,3,3] fp32 (None allowed where the entry allows it), on one device."""
+        self._chk(*mats.values())
+        for name, t in mats.items():
+            if t is not None and tuple(t.shape) != (B, 3, 3):
+                raise PfError(f"{what}: {name} {tuple(t.shape)}, expected {(B, 3, 3)}")
+
+    def ego_accumulate(self, flow, mask, R, sums, weighted: bool, scale_px: float, blocks: int = 0):
+        """pf_ego_accumulate: one pass over flow fp32 [B,2,H,W] (mask uint8 [B,H,W] or None) under R [B,3,3] into sums int64
+        [B,12]; blocks: workgroups per image (0: from the CU count)."""
+        self._have("pf_ego_accumulate")
+        self._chk(flow)
+        if flow.dim() != 4 or flow.shape[1] != 2:
+            raise PfError(f"ego_accumulate: flow {tuple(flow.shape)}, expected [B,2,H,W]")
+        B, _, H, W = flow.shape
+        self._chk_mask(mask, (B, H, W), "ego_accumulate: mask")
+        self._chk_ego_mats(B, "ego_accumulate", R=R)
+        self._chk_bytes(sums, "ego_accumulate: sums", torch.int64)
+        if tuple(sums.shape) != (B, EGO_SUMS) or any(t is not None and t.device != flow.device for t in (mask, R, sums)):
+            raise PfError(f"ego_accumulate: sums {tuple(sums.shape)}, expected {(B, EGO_SUMS)}, every tensor on {flow.device}")
+        self._rc(self._dll.pf_ego_accumulate(_ptr(flow), _ptr(mask), _ptr(R), _ptr(sums), B, H, W, int(bool(weighted)),
+                                             float(scale_px), int(blocks), self._stream(flow)), "pf_ego_accumulate")
+
+    def ego_solve(self, sums, init, R, stats, H: int, W: int, gap_min: float):
+        """pf_ego_solve: R [B,3,3] and stats [B,5] from sums int64 [B,12] (zeroed again); init [B,3,3] or None (identity)."""
+        self._have("pf_ego_solve")
+        self._chk(stats)
+        self._chk_bytes(sums, "ego_solve: sums", torch.int64)
+        if sums.dim() != 2 or sums.shape[1] != EGO_SUMS:
+            raise PfError(f"ego_solve: sums {tuple(sums.shape)}, expected [B,{EGO_SUMS}]")
+        B = sums.shape[0]
+        self._chk_ego_mats(B, "ego_solve", init=init, R=R)
+        if tuple(stats.shape) != (B, EGO_STATS) or any(t is not None and t.device != sums.device for t in (init, R, stats)):
+            raise PfError(f"ego_solve: stats {tuple(stats.shape)}, expected {(B, EGO_STATS)}, every tensor on {sums.device}")
+        self._rc(self._dll.pf_ego_solve(_ptr(sums), _ptr(init), _ptr(R), _ptr(stats), B, int(H), int(W), float(gap_min),
+                                        self._stream(sums)), "pf_ego_solve")
+        return R, stats
+
+    def ego_track(self, R, state, orient, corr, smoothing: float):
+        """pf_ego_track: state float64 [B,8] (two unit quaternions) advanced by R [B,3,3]; writes orient and corr [B,3,3]."""
+        self._have("pf_ego_track")
+        self._chk_bytes(state, "ego_track: state", torch.float64)
+        if state.dim() != 2 or state.shape[1] != EGO_STATE:
+            raise PfError(f"ego_track: state {tuple(state.shape)}, expected [B,{EGO_STATE}]")
+        B = state.shape[0]
+        self._chk_ego_mats(B, "ego_track", R=R, orient=orient, corr=corr)
+        if any(t.device != state.device for t in (R, orient, corr)):
+            raise PfError(f"ego_track: every tensor must be on {state.device}")
+        self._rc(self._dll.pf_ego_track(_ptr(R), _ptr(state), _ptr(orient), _ptr(corr), B, float(smoothing), self._stream(state)),
+                 "pf_ego_track")
+        return orient, corr
+
+    def erp_rotate(self, x, R, out):
+        """pf_erp_rotate: x fp32 [B,C,H,W] or uint8 [B,H,W,C] (C = 1..4) resampled under R [B,3,3] into out (x's shape and dtype)."""
+        self._have("pf_erp_rotate")
+        if x.dim() != 4 or x.dtype not in (torch.float32, torch.uint8) or out.dtype != x.dtype or out.shape != x.shape:
+            raise PfError(f"erp_rotate: x {x.dtype} {tuple(x.shape)} / out {out.dtype} {tuple(out.shape)}, expected fp32 [B,C,H,W] or "
+                          "uint8 [B,H,W,C] and an out like x")
+        self._chk_bytes(x, "erp_rotate: x")
+        self._chk_bytes(out, "erp_rotate: out")
+        if x.dtype == torch.float32:
+            (B, Cc, H, W), form = x.shape, VIEW_F32
+        else:
+            (B, H, W, Cc), form = x.shape, VIEW_U8
+        self._chk_ego_mats(B, "erp_rotate", R=R)
+        if R.device != x.device or out.device != x.device:
+            raise PfError(f"erp_rotate: every tensor must be on {x.device}")
+        self._rc(self._dll.pf_erp_rotate(_ptr(x), _ptr(out), _ptr(R), B, Cc, H, W, form, self._stream(x)), "pf_erp_rotate")
+        return out
+
+    def ego_derotate(self, flow, mask, R, out, valid):
+        """pf_ego_derotate: flow fp32 [B,2,H,W] with the rotation R [B,3,3] removed into out (may be flow); mask, valid: uint8
+        [B,H,W] or None."""
+        self._have("pf_ego_derotate")
+        self._chk(flow, out)
+        if flow.dim() != 4 or flow.shape[1] != 2 or out.shape != flow.shape:
+            raise PfError(f"ego_derotate: flow {tuple(flow.shape)} / out {tuple(out.shape)}, expected [B,2,H,W] twice")
+        B, _, H, W = flow.shape
+        self._chk_mask(mask, (B, H, W), "ego_derotate: mask")
+        self._chk_mask(valid, (B, H, W), "ego_derotate: valid")
+        self._chk_ego_mats(B, "ego_derotate", R=R)
+        if any(t is not None and t.device != flow.device for t in (mask, R, out, valid)):
+            raise PfError(f"ego_derotate: every tensor must be on {flow.device}")
+        self._rc(self._dll.pf_ego_derotate(_ptr(flow), _ptr(mask), _ptr(R), _ptr(out), _ptr(valid), B, H, W, self._stream(flow)),
+                 "pf_ego_derotate")
+        return out, valid
 
     def masked_mean(self, x, mask, out, scratch):
         """out[b] = mean of x[b] over mask[b] == 0 (mask None: everything); scratch: >= 1024 * B bytes."""
