@@ -331,6 +331,43 @@ int pf_erp_rotate(const void* in, void* out, const float* R, int B, int C, int H
 int pf_ego_derotate(const float* flow, const unsigned char* mask, const float* R, float* out, unsigned char* valid, int B, int H, int W,
                     void* stream);
 
+/* Camera translation from 360-degree flow: the epipole, inverse depth up to the baseline, a mask of what moves (DESIGN.md
+ * section 20; the statement is prior-flow_amd/csrc/pf_epipolar.h).  p, q, the left-out rule and the matrices are those of the
+ * block above; the model is q ~ R p + kappa t with t a unit vector [B,3] fp32 in DEVICE memory and kappa = |T| / depth >= 0 (a
+ * point of the scene moves by T in the second frame's axes; the camera centre moves along -R^T t in the first frame's).
+ *
+ * pf_epi_accumulate: one pass over flow [B,2,H,W] (mask [B,H,W] bytes or NULL) under R and t (t NULL: the zero vector, mode
+ *   PF_EPI_T only) into sums [B,22] int64 (pf_epi_sums_bytes; all-zero before the first pass), integers scaled as
+ *   pf_ego_accumulate's.  The weight is cos phi(y) / (1 + e^2 / c^2)^2, e the distance of q from the epipolar great circle of
+ *   r = R p under t (0 while t = 0), c = scale_px 2 pi / W.  mode PF_EPI_T adds M = sum w n^ n^T of the votes
+ *   n^ = n / sqrt(|n|^2 + c_v^2), n = r x q, c_v = vote_px 2 pi / W, D = sum w d, sum w, sum w e^2, sum w |n|^2 and the count
+ *   (sums 0..12); mode PF_EPI_R adds G = sum w g g^T, h = sum w (t . n) g with g = (t . r) q - (r . q) t, sum w and the count (sums
+ *   13..21, 9, 12).  blocks: workgroups per image, 0 = chosen from the CU count.
+ * pf_epi_solve: mode PF_EPI_T: t = the unit eigenvector of M's smallest eigenvalue (3 x 3 cyclic Jacobi in fp64), turned so that
+ *   t . D >= 0; stats [B,6] = {sum w, rms e in pixel widths, used / (H W), gap = (l2 - l1) / (l1 + l2 + l3), parallax rms
+ *   sqrt(sum w |n|^2 / sum w) in pixel widths, valid}; valid = 0 when sum w = 0, gap < gap_min or the parallax rms <
+ *   min_parallax_px, and then t = t_init (NULL: the zero vector).  R may be NULL.  mode PF_EPI_R: dw = -G^-1 h, R <- exp([dw]x) R in
+ *   place; dw = 0 (R untouched) when stats[5] == 0, t = 0 or G's smallest eigenvalue is below 1e-9 of its trace; reads t and
+ *   stats.  Either mode writes zeros over the sums it read.
+ * pf_epi_map: per pixel conf = |q x t|^2, the signed parallax a = (r x q) . (q x t) / |q x t|, inv_depth = a / |q x t|, resid = |e| in
+ *   pixel widths, moving = resid > thr_px or a < -neg_px 2 pi / W; a left-out pixel, conf < conf_min or t = 0 give inv_depth = 0,
+ *   resid = 0, moving = 0 (conf as computed, 0 when left out).  Each of the four outputs [B,H,W] may be NULL.
+ * PF_ERR_BAD_ARG: a NULL flow / R / sums / t / stats where required, sums not 8-byte aligned, outputs aliasing each other or an
+ * input, an unknown mode, blocks outside 0..65535, scale_px or vote_px not positive and finite, a negative or non-finite
+ * gap_min / min_parallax_px / thr_px / neg_px / conf_min.  PF_ERR_BAD_SHAPE as above.  Every refusal answers before anything is
+ * launched.  One launch each, no host read, no allocation, capturable. */
+#define PF_EPI_SUMS 22
+#define PF_EPI_STATS 6
+#define PF_EPI_T 0
+#define PF_EPI_R 1
+long pf_epi_sums_bytes(int B, int H, int W);
+int pf_epi_accumulate(const float* flow, const unsigned char* mask, const float* R, const float* t, void* sums, int B, int H, int W,
+                      int mode, float scale_px, float vote_px, int blocks, void* stream);
+int pf_epi_solve(void* sums, const float* t_init, float* R, float* t, float* stats, int B, int H, int W, int mode, float gap_min,
+                 float min_parallax_px, void* stream);
+int pf_epi_map(const float* flow, const unsigned char* mask, const float* R, const float* t, float* inv_depth, float* resid, float* conf,
+               unsigned char* moving, int B, int H, int W, float thr_px, float neg_px, float conf_min, void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

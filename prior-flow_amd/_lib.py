@@ -188,15 +188,22 @@ _SIGNATURES = {
     "pf_ego_track": [_fp, _fp, _fp, _fp, _i, C.c_float, _fp],
     "pf_erp_rotate": [_fp, _fp, _fp, _i, _i, _i, _i, _i, _fp],
     "pf_ego_derotate": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp],
+    "pf_epi_sums_bytes": [_i, _i, _i],
+    "pf_epi_accumulate": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, C.c_float, C.c_float, _i, _fp],
+    "pf_epi_solve": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, C.c_float, C.c_float, _fp],
+    "pf_epi_map": [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, C.c_float, C.c_float, C.c_float, _fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
 # entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp,
-# pf_emu_splat.cpp, pf_emu_egomotion.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
 _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert",
                   "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp",
                   "pf_splat_scratch_bytes", "pf_splat_accumulate", "pf_splat_resolve",
-                  "pf_ego_scratch_bytes", "pf_ego_accumulate", "pf_ego_solve", "pf_ego_track", "pf_erp_rotate", "pf_ego_derotate")
+                  "pf_ego_scratch_bytes", "pf_ego_accumulate", "pf_ego_solve", "pf_ego_track", "pf_erp_rotate", "pf_ego_derotate",
+                  "pf_epi_sums_bytes", "pf_epi_accumulate", "pf_epi_solve", "pf_epi_map")
 EGO_SUMS, EGO_STATS, EGO_STATE = 12, 5, 8           # PF_EGO_SUMS, PF_EGO_STATS, PF_EGO_STATE
+EPI_SUMS, EPI_STATS = 22, 6                         # PF_EPI_SUMS, PF_EPI_STATS
+EPI_T, EPI_R = 0, 1                                 # PF_EPI_T / PF_EPI_R
 SPLAT_MAX = 4                                       # PF_SPLAT_MAX
 AUG_ROW_WORDS = 32                                  # PF_AUG_ROW_WORDS
 VIEW_MAX, VIEW_WORDS = 16, 12                       # PF_VIEW_MAX, PF_VIEW_WORDS
@@ -282,7 +289,7 @@ class PfLib:
                     continue
                 raise PfError(f"{path} does not export {name}")
             fn.argtypes = args
-            fn.restype = C.c_long if name.endswith(("_ws_floats", "_scratch_bytes")) else _i
+            fn.restype = C.c_long if name.endswith(("_ws_floats", "_scratch_bytes", "_sums_bytes")) else _i
 
     # ---- helpers -----------------------------------------------------------------------------
     def version(self) -> str:
@@ -1339,6 +1346,75 @@ class PfLib:
         self._rc(self._dll.pf_ego_derotate(_ptr(flow), _ptr(mask), _ptr(R), _ptr(out), _ptr(valid), B, H, W, self._stream(flow)),
                  "pf_ego_derotate")
         return out, valid
+
+    # ---- camera translation from 360-degree flow -----------------------
+    def epi_sums_bytes(self, B: int, H: int, W: int) -> int:
+        self._have("pf_epi_sums_bytes")
+        r = self._dll.pf_epi_sums_bytes(B, H, W)
+        self._rc(min(r, 0), "pf_epi_sums_bytes")
+        return r
+
+    def _chk_epi_vecs(self, B, what, **vecs):
+        """Translations [B,3] fp32 (None allowed where the entry allows it)."""
+        self._chk(*vecs.values())
+        for name, t in vecs.items():
+            if t is not None and tuple(t.shape) != (B, 3):
+                raise PfError(f"{what}: {name} {tuple(t.shape)}, expected {(B, 3)}")
+
+    def epi_accumulate(self, flow, mask, R, t, sums, mode: int, scale_px: float, vote_px: float, blocks: int = 0):
+        """pf_epi_accumulate: one pass of `mode` (EPI_T / EPI_R) over flow fp32 [B,2,H,W] (mask uint8 [B,H,W] or None) under R
+        [B,3,3] and t [B,3] (None: zero, EPI_T only) into sums int64 [B,22]; blocks: workgroups per image (0: from the CU count)."""
+        self._have("pf_epi_accumulate")
+        self._chk(flow)
+        if flow.dim() != 4 or flow.shape[1] != 2:
+            raise PfError(f"epi_accumulate: flow {tuple(flow.shape)}, expected [B,2,H,W]")
+        B, _, H, W = flow.shape
+        self._chk_mask(mask, (B, H, W), "epi_accumulate: mask")
+        self._chk_ego_mats(B, "epi_accumulate", R=R)
+        self._chk_epi_vecs(B, "epi_accumulate", t=t)
+        self._chk_bytes(sums, "epi_accumulate: sums", torch.int64)
+        if tuple(sums.shape) != (B, EPI_SUMS) or any(x is not None and x.device != flow.device for x in (mask, R, t, sums)):
+            raise PfError(f"epi_accumulate: sums {tuple(sums.shape)}, expected {(B, EPI_SUMS)}, every tensor on {flow.device}")
+        self._rc(self._dll.pf_epi_accumulate(_ptr(flow), _ptr(mask), _ptr(R), _ptr(t), _ptr(sums), B, H, W, int(mode), float(scale_px),
+                                             float(vote_px), int(blocks), self._stream(flow)), "pf_epi_accumulate")
+
+    def epi_solve(self, sums, t_init, R, t, stats, H: int, W: int, mode: int, gap_min: float, min_parallax_px: float):
+        """pf_epi_solve: EPI_T: t [B,3] and stats [B,6] from sums int64 [B,22]; t_init [B,3] or None (zero); R may be None.
+        EPI_R: R [B,3,3] refined in place about t.  The sums read are zeroed again."""
+        self._have("pf_epi_solve")
+        self._chk(stats)
+        self._chk_bytes(sums, "epi_solve: sums", torch.int64)
+        if sums.dim() != 2 or sums.shape[1] != EPI_SUMS:
+            raise PfError(f"epi_solve: sums {tuple(sums.shape)}, expected [B,{EPI_SUMS}]")
+        B = sums.shape[0]
+        self._chk_ego_mats(B, "epi_solve", R=R)
+        self._chk_epi_vecs(B, "epi_solve", t_init=t_init, t=t)
+        if t is None or tuple(stats.shape) != (B, EPI_STATS) or any(x is not None and x.device != sums.device for x in (t_init, R, t, stats)):
+            raise PfError(f"epi_solve: t is required, stats {tuple(stats.shape)}, expected {(B, EPI_STATS)}, every tensor on {sums.device}")
+        self._rc(self._dll.pf_epi_solve(_ptr(sums), _ptr(t_init), _ptr(R), _ptr(t), _ptr(stats), B, int(H), int(W), int(mode),
+                                        float(gap_min), float(min_parallax_px), self._stream(sums)), "pf_epi_solve")
+        return R, t, stats
+
+    def epi_map(self, flow, mask, R, t, inv_depth, resid, conf, moving, thr_px: float, neg_px: float, conf_min: float):
+        """pf_epi_map: flow fp32 [B,2,H,W] under R [B,3,3] and t [B,3] into inv_depth, resid, conf (fp32 [B,H,W]) and moving (uint8
+        [B,H,W]); each output may be None."""
+        self._have("pf_epi_map")
+        self._chk(flow, inv_depth, resid, conf)
+        if flow.dim() != 4 or flow.shape[1] != 2:
+            raise PfError(f"epi_map: flow {tuple(flow.shape)}, expected [B,2,H,W]")
+        B, _, H, W = flow.shape
+        self._chk_mask(mask, (B, H, W), "epi_map: mask")
+        self._chk_mask(moving, (B, H, W), "epi_map: moving")
+        self._chk_ego_mats(B, "epi_map", R=R)
+        self._chk_epi_vecs(B, "epi_map", t=t)
+        for name, x in (("inv_depth", inv_depth), ("resid", resid), ("conf", conf)):
+            if x is not None and tuple(x.shape) != (B, H, W):
+                raise PfError(f"epi_map: {name} {tuple(x.shape)}, expected {(B, H, W)}")
+        if R is None or t is None or any(x is not None and x.device != flow.device for x in (mask, R, t, inv_depth, resid, conf, moving)):
+            raise PfError(f"epi_map: R and t are required, every tensor on {flow.device}")
+        self._rc(self._dll.pf_epi_map(_ptr(flow), _ptr(mask), _ptr(R), _ptr(t), _ptr(inv_depth), _ptr(resid), _ptr(conf), _ptr(moving),
+                                      B, H, W, float(thr_px), float(neg_px), float(conf_min), self._stream(flow)), "pf_epi_map")
+        return inv_depth, resid, conf, moving
 
     def masked_mean(self, x, mask, out, scratch):
         """out[b] = mean of x[b] over mask[b] == 0 (mask None: everything); scratch: >= 1024 * B bytes."""

@@ -1,0 +1,235 @@
+"""Camera translation from 360-degree flow on an MI355X: pf_epi_accumulate, pf_epi_solve and pf_epi_map on
+the device against the float64 restatement (tests/epipolar_ref.py) under the bounds derived there, launch by launch, and against
+the host emulation of the same header within those bounds (not bit for bit: the two sincosf differ); the truth of the seeded
+scenes; reproducibility under repeated calls and other grids; poisoned buffers; the Python layer (prior_flow_amd.parallax), eager
+and captured, behind a bidirectional FlowStream.  Run with ``-m gpu``."""
+import argparse
+
+import numpy as np
+import pytest
+import torch
+
+import egomotion_ref as er
+import epipolar_cases as pc
+import epipolar_ref as pr
+import golden_cases as gc
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def emu():
+    return pc.emu()
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from prior_flow_amd._lib import load
+    return load()
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def same_bits(a, b, keys=("R", "t", "stats", "R0", "sums", "ego_sums")):
+    return all(np.array_equal(bits(a[k]), bits(b[k])) for k in keys)
+
+
+@pytest.mark.parametrize("H,W", pc.SHAPES + ((40, 1100),))
+def test_device_matches_float64_and_the_emulation(lib, emu, H, W):
+    """Clean scenes at B = 1..3 over both depth fields (with a mask at B = 2), wound columns, junk, end points past a pole and
+    the robust scene: every launch of the device holds the float64 bounds, its map too, and the device's answer lies within the
+    same single-launch bounds of the emulation's."""
+    worst = 0.0
+    cases = [(f"{d} B={B}", pc.scene(B, H, W, d, rot=B)[0], (np.random.default_rng(5).random((B, H, W)) < 0.1).astype(np.uint8) if B == 2 else None)
+             for B, d in ((1, "smooth"), (2, "room"), (3, "smooth"))]
+    if W <= 96:
+        cases.append(("winding", pc.wound_half(pc.scene(2, H, W, "room")[0], 7), None))
+        junk, bad = pc.ec.poison(pc.scene(2, H, W)[0], 5)
+        cases.append(("junk without a mask", junk, None))
+        cases.append(("poles", pc.polar_scene(H, W, 12)[0], None))
+        cases.append(("robust", pc.robust_scene(H, W)[0], None))
+    for name, flow, mask in cases:
+        B = flow.shape[0]
+        steps = pc.stepwise(lib, flow, mask, device="cuda")
+        worst = max(worst, pc.check_steps(steps, flow, mask, what=f"device {name} {H}x{W}"))
+        got = pc.estimate(lib, flow, mask, device="cuda")
+        assert all(np.array_equal(bits(got[k]), bits(steps[-1][i])) for k, i in (("R", 2), ("t", 3), ("stats", 4)))
+        assert not got["sums"].any() and not got["ego_sums"].any()
+        R, t = got["R"], got["t"]
+        pc.check_map(pc.pmap(lib, flow, R, t, mask, "cuda"), flow, R, t, pr.parallax(flow, R, t, mask), f"device map {name} {H}x{W}")
+        # against the emulation: the last T pass of both, from the device's state before it, within the restatement's bound
+        e = pc.estimate(emu, flow, mask)
+        ref = pr.Pose(B, H, W)
+        _, rt, rst = ref.step("T", False, flow, mask, steps[-2][2].astype(np.float64), steps[-2][3].astype(np.float64), None)
+        assert np.array_equal(e["stats"][:, 5], got["stats"][:, 5]) and np.array_equal(bits(e["stats"][:, 2]), bits(got["stats"][:, 2]))
+        for b in range(B):
+            if rst[b, 5]:
+                assert pr.angle_vec(e["t"][b], t[b]) <= 2 * pr.t_pass_bound(rst[b], ref.last_t[b], W), (name, b)
+    print(f"[epipolar] device {H}x{W}: worst error / bound {worst:.2e}")
+
+
+@pytest.mark.parametrize("H,W", ((32, 64), (48, 96)))
+def test_device_against_the_truth(lib, H, W):
+    """The caps of the restatement's truth checks, on the device: clean scenes t <= 0.5 px and R no worse than the rotation-only
+    fit; the robust scene at vote_px 0.1 and 0.5: t <= 0.5 px, recall >= 0.9, false alarms <= 0.002."""
+    for depth in ("smooth", "room"):
+        for rot in range(3):
+            flow, R_true, t_true, _ = pc.scene(3, H, W, depth, rot=rot, base=rot)
+            got = pc.estimate(lib, flow, device="cuda")
+            for b in range(3):
+                et = pr.px(pr.angle_vec(got["t"][b], t_true[b]), W)
+                eR, eR0 = er.angle_between(got["R"][b], R_true[b]), er.angle_between(got["R0"][b], R_true[b])
+                assert et <= 0.5 and eR <= eR0, (depth, rot, b, et, eR, eR0)
+    flow, R_true, t_true, blk = pc.robust_scene(H, W)
+    for vote_px in (0.1, 0.5):
+        got = pc.estimate(lib, flow, device="cuda", vote_px=vote_px)
+        mov = pc.pmap(lib, flow, got["R"], got["t"], device="cuda")[3]
+        et, recall, false = pr.px(pr.angle_vec(got["t"][0], t_true), W), float(mov[0][blk].mean()), float(mov[0][~blk].mean())
+        print(f"[epipolar] device robust {H}x{W} vote_px {vote_px}: t {et:.4f} px, recall {recall:.3f}, false {false:.5f}")
+        assert et <= 0.5 and recall >= 0.9 and false <= 0.002
+
+
+def test_device_degenerate_inputs(lib):
+    B, H, W = 2, 32, 64
+    t_init = np.array([[0.6, 0, 0.8], [0, 1, 0]], np.float32)
+    for flow in (pc.ec.rotation_flows(B, H, W)[0], np.zeros((B, 2, H, W), np.float32)):
+        for init in (None, t_init):
+            got = pc.estimate(lib, flow, init_t=init, device="cuda")
+            assert not got["stats"][:, 5].any()
+            assert np.array_equal(got["t"], np.zeros((B, 3), np.float32) if init is None else init)
+            assert np.array_equal(bits(got["R"]), bits(got["R0"]))
+        k, r, c, m = pc.pmap(lib, flow, got["R"], np.zeros((B, 3)), device="cuda")
+        assert not k.any() and not r.any() and not c.any() and not m.any()
+    flow, R, t, _ = pc.scene(B, H, W)
+    mask = np.ones((B, H, W), np.uint8)
+    for mode in (0, 1):
+        assert not pc.raw_sums(lib, flow, R, t, mode, mask, "cuda").any()
+    junk, bad = pc.ec.poison(flow, 3)
+    clean = np.where(bad[:, None] != 0, np.float32(0), flow)
+    assert same_bits(pc.estimate(lib, junk, device="cuda"), pc.estimate(lib, clean, bad, device="cuda"))
+    a, b = pc.pmap(lib, junk, R, t, device="cuda"), pc.pmap(lib, clean, R, t, bad, "cuda")
+    assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(a, b))
+
+
+def test_same_bits_on_every_run_and_for_every_grid(lib):
+    """Two runs, and grids of 1, 3 and 64 workgroups per image against the one chosen from the CU count: the raw sums of a T and
+    of an R pass, t, R and the stats are the same bits.  33x70 on one workgroup is 33 strips for 16 waves and 40x1100 nine strips to
+    a row, the last one ragged: the strided loop and the tail of a row both run."""
+    for (H, W), B in (((33, 70), 3), ((40, 1100), 2), ((6, 10), 1)):
+        flow, R, t, _ = pc.scene(B, H, W)
+        flow, bad = pc.ec.poison(flow, 3)
+        want = None
+        for blocks in (0, 0, 1, 3, 64):
+            got = [pc.raw_sums(lib, flow, R, t, 0, bad, "cuda", blocks=blocks), pc.raw_sums(lib, flow, R, t, 1, bad, "cuda", blocks=blocks),
+                   pc.raw_sums(lib, flow, R, None, 0, bad, "cuda", blocks=blocks)]
+            e = pc.estimate(lib, flow, bad, device="cuda", blocks=blocks)
+            got += [e["R"], e["t"], e["stats"]]
+            assert got[0].any() and got[1].any()
+            want = got if want is None else want
+            assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(got, want)), ((H, W), blocks)
+
+
+def test_poisoned_buffers_give_the_bits_of_a_fresh_estimator(lib):
+    B, H, W = 2, 33, 70
+    flow, _, _, _ = pc.scene(B, H, W)
+    fresh = pc.estimate(lib, flow, device="cuda")
+    for junk, isum in ((float("nan"), 0x7FF8123456789ABC), (1e30, 2 ** 62), (-1e30, -2 ** 62)):
+        est = pc.estimator(lib, B, H, W, "cuda")
+        for buf in (est.R, est.t, est.stats, est.estimator.R, est.estimator.stats):
+            buf.fill_(junk)
+        est.sums.fill_(isum)
+        est.estimator.sums.fill_(isum)
+        assert same_bits(pc.estimate(lib, flow, device="cuda", est=est), fresh), junk
+
+
+def test_python_layer_on_the_device():
+    from prior_flow_amd._lib import PfError
+    from prior_flow_amd.parallax import PoseEstimator, parallax_map
+    B, H, W = 1, 8, 16
+    z = torch.zeros(B, 2, H, W, device="cuda")
+    est = PoseEstimator(B, H, W, "cuda")
+    R, t = est.estimate(z)
+    assert not bool(est.stats[:, 5].any()) and not bool(t.any())
+    out = parallax_map(z, R, t)
+    assert [o.dtype for o in out] == [torch.float32] * 3 + [torch.uint8] and not any(bool(o.any()) for o in out)
+    for bad in (lambda: est.estimate(z.cpu()), lambda: est.estimate(z, mask=torch.zeros(B, H, W, device="cuda")),
+                lambda: est.estimate(z, init_t=t), lambda: est.estimate(z, init_t=torch.zeros(B, 3)),
+                lambda: parallax_map(z.cpu(), R.cpu(), t.cpu()), lambda: parallax_map(z, R, t.cpu()),
+                lambda: parallax_map(z, R, t, out=(out[0], out[1], out[2])), lambda: PoseEstimator(B, H, W, "cpu"),
+                lambda: PoseEstimator(B, H, W, "cuda", rounds=0)):
+        with pytest.raises(PfError):
+            bad()
+
+
+# ---- behind the bidirectional stream ---------------------------------------------------------------------------------------------
+def test_pose_behind_the_stream_eager_and_captured():
+    """A four-frame 128x256 sequence on the tiny model, iters = 2, occlusion "plane": estimate_bidirectional equals the entry
+    points called one by one bit for bit and allocates nothing; the estimate of the last pair plus parallax_map, captured into ONE
+    graph and replayed twice on copied-in inputs, gives the eager call's bits.  The capture runs with torch's global error mode,
+    under which a synchronisation inside the region raises."""
+    from prior_flow_amd.modules import state_dict_shapes
+    from prior_flow_amd.parallax import PoseEstimator, parallax_map
+    from prior_flow_amd.prior_raft import PriOr_RAFT
+    from prior_flow_amd.video import BidirectionalFlow, FlowStream
+    B, H, W = 1, 128, 256
+    m = PriOr_RAFT(argparse.Namespace(mixed_precision=False, dropout=0.0, alternate_corr=False))
+    m.load_state_dict(gc.det_state_dict(state_dict_shapes()), strict=True)
+    m = m.cuda().eval()
+    f0, _ = gc.synthetic_pair(B, H, W, seed=5)
+    frames = [torch.roll(f0, shifts=(t, 3 * t), dims=(2, 3)).cuda().contiguous() for t in range(4)]
+    stream = FlowStream(m, iters=2, bidirectional=True, occlusion="plane")
+    pose = PoseEstimator(B, H, W, "cuda")
+    lib = pose.lib
+    results = []
+    with torch.no_grad():
+        for frame in frames:
+            r = stream(frame)
+            if r is None:
+                continue
+            r = BidirectionalFlow(*[t.clone() if t is not None else None for t in r])
+            torch.cuda.synchronize()
+            n0 = torch.cuda.memory_stats()["allocation.all.allocated"]
+            R, t = pose.estimate_bidirectional(r)
+            assert torch.cuda.memory_stats()["allocation.all.allocated"] == n0, "an estimate allocated device memory"
+            steps = pc.stepwise(lib, r.forward.cpu().numpy(), r.occ_forward.cpu().numpy(), device="cuda")
+            assert np.array_equal(bits(R.cpu().numpy()), bits(steps[-1][2])) and np.array_equal(bits(t.cpu().numpy()), bits(steps[-1][3]))
+            assert np.array_equal(bits(pose.stats.cpu().numpy()), bits(steps[-1][4])) and not pose.sums.any()
+            assert np.array_equal(bits(pose.estimator.R.cpu().numpy()), bits(steps[0][2]))
+            results.append(r)
+    assert len(results) == 3
+    print(f"[epipolar] behind the stream: stats of the last pair {pose.stats[0].tolist()}")
+    last = results[2]
+    eager = PoseEstimator(B, H, W, "cuda")
+    R, t = eager.estimate_bidirectional(last)
+    want = [x.clone() for x in (R, t, eager.stats) + tuple(parallax_map(last.forward, R, t, mask=last.occ_forward))]
+    cap = PoseEstimator(B, H, W, "cuda")
+    src = BidirectionalFlow(*[torch.zeros_like(x) if x is not None else None for x in last])
+    outs = tuple(torch.zeros(B, H, W, device="cuda") for _ in range(3)) + (torch.zeros(B, H, W, dtype=torch.uint8, device="cuda"),)
+
+    def run():
+        Rc, tc = cap.estimate_bidirectional(src)
+        parallax_map(src.forward, Rc, tc, mask=src.occ_forward, out=outs)
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        run()                                                     # warm-up on the side stream
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        run()
+    for s, x in zip(src, last):
+        if s is not None:
+            s.copy_(x)
+    for _ in range(2):
+        for buf in (cap.R, cap.t, cap.stats) + outs[:3]:
+            buf.fill_(float("nan"))
+        cap.sums.fill_(-1)
+        cap.estimator.sums.fill_(-1)
+        graph.replay()
+        torch.cuda.synchronize()
+        got = (cap.R, cap.t, cap.stats) + outs
+        assert all(torch.equal(x, y) for x, y in zip(got, want)) and not cap.sums.any()
