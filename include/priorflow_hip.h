@@ -809,6 +809,23 @@ int pf_seq_loss_batch(const float* const* preds, const float* gt, const float* v
                       const float* i_weights, float max_flow, float* const* grads, double* partials, int nblk, int n,
                       int B, int N, void* stream);
 
+/* Self-supervised criterion of one branch (the statement is csrc/pf_selfsup.h): for each of the n <= 32
+ * predictions preds[i] [B,2,H,W] (pixels) the photometric term -- image2 [B,3,H,W] (0..255) sampled at p + f with the taps of
+ * pf_cycle_warp, against image1, Charbonnier with eps_photo, weighted by weight [H*W] -- and the first-order edge-aware
+ * smoothness term (pairs to the right, the seam included, and downwards; Charbonnier with eps_smooth; edges of image1 through
+ * exp(-edge_lambda |dI| / 255)), both divided by z = B * sum weight.  mask [B,H,W] bytes or NULL: a non-zero byte leaves the
+ * pixel's photometric term out; so does a flow that is not finite or has |u| or |v| >= max_flow, which also drops the pixel's
+ * smoothness pairs.  grads[i] (optional) = i_weights[i] * d (w_photo photo_i + w_smooth smooth_i) / d preds[i], every element
+ * written.  partials [n][B][nblk][4] fp64 = {photo, smooth, sum of weight over the pixels used, count of left-out flows} per chunk
+ * of ceil(H * W / nblk) consecutive pixels; the caller adds the chunks.  preds / grads / i_weights are HOST arrays as in
+ * pf_seq_loss_batch.  blocks: workgroups of the launch, 0 = one per (chunk, image); neither the gradients nor the partials depend
+ * on it.  PF_ERR_BAD_ARG: a NULL where one is required, an output whose bytes meet those of an input or of another output, a
+ * scalar out of range (an eps whose square underflows, a max_flow that is not finite), blocks outside 0..65536.  PF_ERR_BAD_SHAPE: B < 1, H or W < 2, H * W >= 2^30, n outside 1..32, nblk outside 1..4096. */
+int pf_selfsup_loss_batch(const float* const* preds, const float* image1, const float* image2, const float* weight,
+                          const unsigned char* mask, const float* i_weights, float* const* grads, double* partials, int nblk,
+                          int n, int B, int H, int W, float w_photo, float w_smooth, float eps_photo, float eps_smooth,
+                          float edge_lambda, float max_flow, float z, int blocks, void* stream);
+
 /* partials[k] = sum of squares of chunk k of x[0..n): the total norm of `clip_grad_norm_` (train_flow.py:137). */
 int pf_sum_squares(const float* x, long n, double* partials, int nblk, void* stream);
 

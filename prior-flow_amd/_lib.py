@@ -192,18 +192,20 @@ _SIGNATURES = {
     "pf_epi_accumulate": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, C.c_float, C.c_float, _i, _fp],
     "pf_epi_solve": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, C.c_float, C.c_float, _fp],
     "pf_epi_map": [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, C.c_float, C.c_float, C.c_float, _fp],
+    "pf_selfsup_loss_batch": [_fp] * 8 + [_i] * 5 + [C.c_float] * 7 + [_i, _fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
 # entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp,
-# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
 _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert",
                   "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp",
                   "pf_splat_scratch_bytes", "pf_splat_accumulate", "pf_splat_resolve",
                   "pf_ego_scratch_bytes", "pf_ego_accumulate", "pf_ego_solve", "pf_ego_track", "pf_erp_rotate", "pf_ego_derotate",
-                  "pf_epi_sums_bytes", "pf_epi_accumulate", "pf_epi_solve", "pf_epi_map")
+                  "pf_epi_sums_bytes", "pf_epi_accumulate", "pf_epi_solve", "pf_epi_map", "pf_selfsup_loss_batch")
 EGO_SUMS, EGO_STATS, EGO_STATE = 12, 5, 8           # PF_EGO_SUMS, PF_EGO_STATS, PF_EGO_STATE
 EPI_SUMS, EPI_STATS = 22, 6                         # PF_EPI_SUMS, PF_EPI_STATS
 EPI_T, EPI_R = 0, 1                                 # PF_EPI_T / PF_EPI_R
+SS_MAX, SS_SUMS = 32, 4                             # PF_SS_MAX, PF_SS_SUMS
 SPLAT_MAX = 4                                       # PF_SPLAT_MAX
 AUG_ROW_WORDS = 32                                  # PF_AUG_ROW_WORDS
 VIEW_MAX, VIEW_WORDS = 16, 12                       # PF_VIEW_MAX, PF_VIEW_WORDS
@@ -1415,6 +1417,39 @@ class PfLib:
         self._rc(self._dll.pf_epi_map(_ptr(flow), _ptr(mask), _ptr(R), _ptr(t), _ptr(inv_depth), _ptr(resid), _ptr(conf), _ptr(moving),
                                       B, H, W, float(thr_px), float(neg_px), float(conf_min), self._stream(flow)), "pf_epi_map")
         return inv_depth, resid, conf, moving
+
+    # ---- self-supervised criterion --------------------------------------
+    def selfsup_loss_batch(self, preds, image1, image2, weight, mask, i_weights, grads, partials, z: float, w_photo: float,
+                           w_smooth: float, eps_photo: float, eps_smooth: float, edge_lambda: float, max_flow: float, blocks: int = 0):
+        """pf_selfsup_loss_batch: the n <= 32 predictions preds[i] fp32 [B,2,H,W] against image1 / image2 fp32 [B,3,H,W], weight fp32
+        [H*W], mask uint8 [B,H,W] or None; grads: None, or a list of n tensors like preds[i] (single entries may be None);
+        partials float64 [n, B, nblk, 4]; z = B * sum weight; blocks: workgroups of the launch (0: one per chunk and image)."""
+        self._have("pf_selfsup_loss_batch")
+        n = len(preds)
+        if not 1 <= n <= SS_MAX:
+            raise PfError(f"selfsup_loss_batch: {n} predictions, expected 1..{SS_MAX}")
+        self._chk(image1, image2, weight, *preds, *(g for g in (grads or ()) if g is not None))
+        if image1.dim() != 4 or image1.shape[1] != 3 or image2.shape != image1.shape:
+            raise PfError(f"selfsup_loss_batch: image1 {tuple(image1.shape)} / image2 {tuple(image2.shape)}, expected [B,3,H,W] twice")
+        B, _, H, W = image1.shape
+        want = (B, 2, H, W)
+        if any(tuple(p.shape) != want for p in preds) or weight.numel() != H * W \
+                or (grads is not None and (len(grads) != n or any(g is not None and tuple(g.shape) != want for g in grads))):
+            raise PfError(f"selfsup_loss_batch: predictions and gradients must be {want}, weight must hold {H * W} values")
+        self._chk_mask(mask, (B, H, W), "selfsup_loss_batch: mask")
+        if partials.dtype != torch.float64 or partials.dim() != 4 or tuple(partials.shape[:2]) != (n, B) or partials.shape[3] != SS_SUMS \
+                or not partials.is_contiguous():
+            raise PfError(f"selfsup_loss_batch: partials must be contiguous float64 [n, B, nblk, {SS_SUMS}]")
+        others = [image2, weight, mask, partials, *preds, *(g for g in (grads or ()) if g is not None)]
+        if any(t is not None and t.device != image1.device for t in others):
+            raise PfError(f"selfsup_loss_batch: every tensor must be on {image1.device}")
+        pa = (C.c_void_p * n)(*[p.data_ptr() for p in preds])
+        ga = (C.c_void_p * n)(*[None if g is None else g.data_ptr() for g in grads]) if grads is not None else None
+        wa = (C.c_float * n)(*[float(w) for w in i_weights])
+        self._rc(self._dll.pf_selfsup_loss_batch(pa, _ptr(image1), _ptr(image2), _ptr(weight), _ptr(mask), wa, ga,
+                                                 C.c_void_p(partials.data_ptr()), partials.shape[2], n, B, H, W, float(w_photo),
+                                                 float(w_smooth), float(eps_photo), float(eps_smooth), float(edge_lambda),
+                                                 float(max_flow), float(z), int(blocks), self._stream(image1)), "pf_selfsup_loss_batch")
 
     def masked_mean(self, x, mask, out, scratch):
         """out[b] = mean of x[b] over mask[b] == 0 (mask None: everything); scratch: >= 1024 * B bytes."""
