@@ -368,6 +368,51 @@ int pf_epi_solve(void* sums, const float* t_init, float* R, float* t, float* sta
 int pf_epi_map(const float* flow, const unsigned char* mask, const float* R, const float* t, float* inv_depth, float* resid, float* conf,
                unsigned char* moving, int B, int H, int W, float thr_px, float neg_px, float conf_min, void* stream);
 
+/* Camera trajectory from 360-degree video: the scale link between consecutive pairs, the pose chain and depth fused in one unit
+ * (the statement is prior-flow_amd/csrc/pf_odometry.h).  A MAP is what pf_epi_map writes: inv_depth (kappa),
+ * conf fp32 [B,H,W] and moving bytes [B,H,W].  Map a and map b lie on ONE grid, the grid of the frame two consecutive pairs share:
+ * a of the earlier pair's backward flow under its reversed pose, b of the later pair's forward flow, so kappa_b / kappa_a is the
+ * ratio of the two baselines at every static pixel.
+ *
+ * pf_odo_accumulate: the pixels of both maps into hist [B, 2 bins + 2] int64 (pf_odo_hist_bytes; all-zero before the call).  A pixel
+ *   is left out when a moving byte is non-zero, !(conf > 0) or !(kappa_min <= kappa < 2^30) for either map.  Otherwise
+ *   w = cos phi(y) min(conf_a, 1) min(conf_b, 1), l = log2(kappa_b / kappa_a) clamped to +-log2_range, bin = floor((l + L) bins /
+ *   (2 L)) clamped to 0..bins-1; W[bin] += w, M[bin] += w l / L, total += w (integers scaled by 2^S as pf_ego_accumulate's), count
+ *   += 1.  blocks: workgroups per image, 0 = chosen from the CU count.
+ * pf_odo_solve: on the integers: the median bin m (the smallest whose inclusive prefix sum C has 2 C >= total), the quartile bins
+ *   likewise, l^ = L sum M / sum W over bins m +- trim_bins (cut to the range), ratio [B] = exp2(l^); stats [B,6] = {sum w, used /
+ *   (H W), l^, iqr = (q3 - q1) 2 L / bins, window weight / total, valid}.  valid = 0 and ratio = 1 when nothing counted, used / (H W)
+ *   < min_used, iqr > max_iqr or m is the first or the last bin.  Every cell is written back as zero.
+ * pf_odo_reverse_pose: (R, t) -> (R^T, -R^T t), t = 0 stays +0.
+ * pf_odo_track: state [B,12] fp64 = {A (unit quaternion), b[3], S, steps, segment, prev_valid, 0}, {1,0,0,0, 0,0,0, 1, 0,0,0, 0} at
+ *   the start.  A <- q(R) A, b <- R b; with pose_stats[5] != 0: S <- S ratio when the pair before was valid and link_stats[5] != 0,
+ *   otherwise S stays and segment += 1; then b <- b + S t.  orient [B,3,3] = A, centre [B,3] = -A^T b, baseline [B] = S, flags
+ *   [B,4] int32 = {steps, segment, pose valid, link valid}.
+ * pf_odo_fuse: a map counts at a pixel where moving == 0, conf >= conf_min and 0 <= kappa < 2^30 (map a only where link_valid[b] !=
+ *   0) with weight conf; d = kappa / S; inv_depth = (w_a d_a + w_b d_b) / (w_a + w_b), weight = w_a + w_b, both 0 where nothing counts or the
+ *   weight sum is not positive and finite;
+ *   disagree = both count, both kappa >= kappa_min and |log2(d_b / d_a)| > tol_log2.  S_a, S_b, link_valid: fp32 [B] in DEVICE
+ *   memory.  Each of the three outputs [B,H,W] may be NULL.
+ * PF_ERR_BAD_ARG: a NULL input or required output, hist / state not 8-byte aligned, an output whose bytes meet an input's or another
+ * output's, bins not a power of two in 64..1024, blocks outside 0..65535, trim_bins outside 0..bins, log2_range / kappa_min / max_iqr /
+ * tol_log2 not positive and finite (log2_range at most 64), a negative or non-finite min_used / conf_min.  PF_ERR_BAD_SHAPE as
+ * above.  Every refusal answers before anything is launched.  One launch each, no host read, no allocation, capturable. */
+#define PF_ODO_STATS 6
+#define PF_ODO_STATE 12
+#define PF_ODO_FLAGS 4
+long pf_odo_hist_bytes(int B, int H, int W, int bins);
+int pf_odo_accumulate(const float* inv_a, const float* conf_a, const unsigned char* moving_a, const float* inv_b, const float* conf_b,
+                      const unsigned char* moving_b, void* hist, int B, int H, int W, int bins, float log2_range, float kappa_min,
+                      int blocks, void* stream);
+int pf_odo_solve(void* hist, float* ratio, float* stats, int B, int H, int W, int bins, float log2_range, int trim_bins, float min_used,
+                 float max_iqr, void* stream);
+int pf_odo_reverse_pose(const float* R, const float* t, float* R_rev, float* t_rev, int B, void* stream);
+int pf_odo_track(const float* R, const float* t, const float* pose_stats, const float* ratio, const float* link_stats, void* state,
+                 float* orient, float* centre, float* baseline, int* flags, int B, void* stream);
+int pf_odo_fuse(const float* inv_a, const float* conf_a, const unsigned char* moving_a, const float* inv_b, const float* conf_b,
+                const unsigned char* moving_b, const float* S_a, const float* S_b, const float* link_valid, float* inv_depth,
+                float* weight, unsigned char* disagree, int B, int H, int W, float conf_min, float kappa_min, float tol_log2, void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

@@ -192,19 +192,27 @@ _SIGNATURES = {
     "pf_epi_accumulate": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, C.c_float, C.c_float, _i, _fp],
     "pf_epi_solve": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, C.c_float, C.c_float, _fp],
     "pf_epi_map": [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, C.c_float, C.c_float, C.c_float, _fp],
+    "pf_odo_hist_bytes": [_i, _i, _i, _i],
+    "pf_odo_accumulate": [_fp] * 7 + [_i] * 4 + [C.c_float, C.c_float, _i, _fp],
+    "pf_odo_solve": [_fp, _fp, _fp, _i, _i, _i, _i, C.c_float, _i, C.c_float, C.c_float, _fp],
+    "pf_odo_reverse_pose": [_fp, _fp, _fp, _fp, _i, _fp],
+    "pf_odo_track": [_fp] * 10 + [_i, _fp],
+    "pf_odo_fuse": [_fp] * 12 + [_i, _i, _i, C.c_float, C.c_float, C.c_float, _fp],
     "pf_selfsup_loss_batch": [_fp] * 8 + [_i] * 5 + [C.c_float] * 7 + [_i, _fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
 # entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp,
-# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp, pf_emu_odometry.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
 _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert",
                   "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp",
                   "pf_splat_scratch_bytes", "pf_splat_accumulate", "pf_splat_resolve",
                   "pf_ego_scratch_bytes", "pf_ego_accumulate", "pf_ego_solve", "pf_ego_track", "pf_erp_rotate", "pf_ego_derotate",
-                  "pf_epi_sums_bytes", "pf_epi_accumulate", "pf_epi_solve", "pf_epi_map", "pf_selfsup_loss_batch")
+                  "pf_epi_sums_bytes", "pf_epi_accumulate", "pf_epi_solve", "pf_epi_map", "pf_selfsup_loss_batch",
+                  "pf_odo_hist_bytes", "pf_odo_accumulate", "pf_odo_solve", "pf_odo_reverse_pose", "pf_odo_track", "pf_odo_fuse")
 EGO_SUMS, EGO_STATS, EGO_STATE = 12, 5, 8           # PF_EGO_SUMS, PF_EGO_STATS, PF_EGO_STATE
 EPI_SUMS, EPI_STATS = 22, 6                         # PF_EPI_SUMS, PF_EPI_STATS
 EPI_T, EPI_R = 0, 1                                 # PF_EPI_T / PF_EPI_R
+ODO_STATS, ODO_STATE, ODO_FLAGS = 6, 12, 4          # PF_ODO_STATS, PF_ODO_STATE, PF_ODO_FLAGS
 SS_MAX, SS_SUMS = 32, 4                             # PF_SS_MAX, PF_SS_SUMS
 SPLAT_MAX = 4                                       # PF_SPLAT_MAX
 AUG_ROW_WORDS = 32                                  # PF_AUG_ROW_WORDS
@@ -291,7 +299,7 @@ class PfLib:
                     continue
                 raise PfError(f"{path} does not export {name}")
             fn.argtypes = args
-            fn.restype = C.c_long if name.endswith(("_ws_floats", "_scratch_bytes", "_sums_bytes")) else _i
+            fn.restype = C.c_long if name.endswith(("_ws_floats", "_scratch_bytes", "_sums_bytes", "_hist_bytes")) else _i
 
     # ---- helpers -----------------------------------------------------------------------------
     def version(self) -> str:
@@ -1417,6 +1425,112 @@ class PfLib:
         self._rc(self._dll.pf_epi_map(_ptr(flow), _ptr(mask), _ptr(R), _ptr(t), _ptr(inv_depth), _ptr(resid), _ptr(conf), _ptr(moving),
                                       B, H, W, float(thr_px), float(neg_px), float(conf_min), self._stream(flow)), "pf_epi_map")
         return inv_depth, resid, conf, moving
+
+    # ---- camera trajectory ----------------------------------------------
+    def odo_hist_bytes(self, B: int, H: int, W: int, bins: int) -> int:
+        self._have("pf_odo_hist_bytes")
+        r = self._dll.pf_odo_hist_bytes(B, H, W, int(bins))
+        self._rc(min(r, 0), "pf_odo_hist_bytes")
+        return r
+
+    def _chk_odo_map(self, m, what):
+        """A parallax map (inv_depth, conf fp32 [B,H,W], moving uint8 [B,H,W]) -> its shape."""
+        if not isinstance(m, (tuple, list)) or len(m) != 3 or not all(isinstance(x, torch.Tensor) for x in m):
+            raise PfError(f"{what}: a map is (inv_depth, conf, moving)")
+        self._chk(m[0], m[1])
+        if m[0].dim() != 3 or m[1].shape != m[0].shape or m[1].device != m[0].device or m[2].device != m[0].device:
+            raise PfError(f"{what}: inv_depth {tuple(m[0].shape)}, conf {tuple(m[1].shape)}, expected two [B,H,W] on one device")
+        self._chk_mask(m[2], m[0].shape, f"{what}: moving")
+        return tuple(m[0].shape)
+
+    def _chk_odo_vec(self, t, shape, what, dtype=torch.float32):
+        self._chk_bytes(t, what, dtype)
+        if tuple(t.shape) != tuple(shape):
+            raise PfError(f"{what}: {tuple(t.shape)}, expected {tuple(shape)}")
+
+    def odo_accumulate(self, map_a, map_b, hist, bins: int, log2_range: float, kappa_min: float, blocks: int = 0):
+        """pf_odo_accumulate: the pixels of two maps (inv_depth, conf, moving) of one grid into hist int64 [B, 2 bins + 2]."""
+        self._have("pf_odo_accumulate")
+        B, H, W = self._chk_odo_map(map_a, "odo_accumulate: map_a")
+        if self._chk_odo_map(map_b, "odo_accumulate: map_b") != (B, H, W) or map_b[0].device != map_a[0].device:
+            raise PfError("odo_accumulate: the two maps differ in shape or device")
+        self._chk_odo_vec(hist, (B, 2 * int(bins) + 2), "odo_accumulate: hist", torch.int64)
+        if hist.device != map_a[0].device:
+            raise PfError(f"odo_accumulate: every tensor must be on {map_a[0].device}")
+        self._rc(self._dll.pf_odo_accumulate(_ptr(map_a[0]), _ptr(map_a[1]), _ptr(map_a[2]), _ptr(map_b[0]), _ptr(map_b[1]), _ptr(map_b[2]),
+                                             _ptr(hist), B, H, W, int(bins), float(log2_range), float(kappa_min), int(blocks),
+                                             self._stream(hist)), "pf_odo_accumulate")
+
+    def odo_solve(self, hist, ratio, stats, H: int, W: int, bins: int, log2_range: float, trim_bins: int, min_used: float, max_iqr: float):
+        """pf_odo_solve: ratio [B] and stats [B,6] from hist int64 [B, 2 bins + 2], which is zeroed again."""
+        self._have("pf_odo_solve")
+        self._chk_bytes(hist, "odo_solve: hist", torch.int64)
+        if hist.dim() != 2 or hist.shape[1] != 2 * int(bins) + 2:
+            raise PfError(f"odo_solve: hist {tuple(hist.shape)}, expected [B,{2 * int(bins) + 2}]")
+        B = hist.shape[0]
+        self._chk_odo_vec(ratio, (B,), "odo_solve: ratio")
+        self._chk_odo_vec(stats, (B, ODO_STATS), "odo_solve: stats")
+        if ratio.device != hist.device or stats.device != hist.device:
+            raise PfError(f"odo_solve: every tensor must be on {hist.device}")
+        self._rc(self._dll.pf_odo_solve(_ptr(hist), _ptr(ratio), _ptr(stats), B, int(H), int(W), int(bins), float(log2_range), int(trim_bins),
+                                        float(min_used), float(max_iqr), self._stream(hist)), "pf_odo_solve")
+        return ratio, stats
+
+    def odo_reverse_pose(self, R, t, R_rev, t_rev):
+        """pf_odo_reverse_pose: (R [B,3,3], t [B,3]) -> (R^T, -R^T t) into R_rev, t_rev."""
+        self._have("pf_odo_reverse_pose")
+        self._chk(R)
+        if R.dim() != 3:
+            raise PfError(f"odo_reverse_pose: R {tuple(R.shape)}, expected [B,3,3]")
+        B = R.shape[0]
+        self._chk_ego_mats(B, "odo_reverse_pose", R=R, R_rev=R_rev)
+        self._chk_epi_vecs(B, "odo_reverse_pose", t=t, t_rev=t_rev)
+        if any(x is None or x.device != R.device for x in (t, R_rev, t_rev)):
+            raise PfError(f"odo_reverse_pose: every tensor is required, on {R.device}")
+        self._rc(self._dll.pf_odo_reverse_pose(_ptr(R), _ptr(t), _ptr(R_rev), _ptr(t_rev), B, self._stream(R)), "pf_odo_reverse_pose")
+        return R_rev, t_rev
+
+    def odo_track(self, R, t, pose_stats, ratio, link_stats, state, orient, centre, baseline, flags):
+        """pf_odo_track: state float64 [B,12] advanced by one pair; writes orient [B,3,3], centre [B,3], baseline [B], flags int32 [B,4]."""
+        self._have("pf_odo_track")
+        self._chk_bytes(state, "odo_track: state", torch.float64)
+        if state.dim() != 2 or state.shape[1] != ODO_STATE:
+            raise PfError(f"odo_track: state {tuple(state.shape)}, expected [B,{ODO_STATE}]")
+        B = state.shape[0]
+        self._chk_ego_mats(B, "odo_track", R=R, orient=orient)
+        self._chk_epi_vecs(B, "odo_track", t=t, centre=centre)
+        self._chk_odo_vec(pose_stats, (B, EPI_STATS), "odo_track: pose_stats")
+        self._chk_odo_vec(link_stats, (B, ODO_STATS), "odo_track: link_stats")
+        self._chk_odo_vec(ratio, (B,), "odo_track: ratio")
+        self._chk_odo_vec(baseline, (B,), "odo_track: baseline")
+        self._chk_odo_vec(flags, (B, ODO_FLAGS), "odo_track: flags", torch.int32)
+        if any(x is None or x.device != state.device for x in (R, t, pose_stats, ratio, link_stats, orient, centre, baseline, flags)):
+            raise PfError(f"odo_track: every tensor is required, on {state.device}")
+        self._rc(self._dll.pf_odo_track(_ptr(R), _ptr(t), _ptr(pose_stats), _ptr(ratio), _ptr(link_stats), _ptr(state), _ptr(orient),
+                                        _ptr(centre), _ptr(baseline), _ptr(flags), B, self._stream(state)), "pf_odo_track")
+        return orient, centre
+
+    def odo_fuse(self, map_a, map_b, S_a, S_b, link_valid, inv_depth, weight, disagree, conf_min: float, kappa_min: float, tol_log2: float):
+        """pf_odo_fuse: two maps of one grid, brought to one unit by the device scalars S_a, S_b [B] (map a only where link_valid
+        [B] != 0), into inv_depth, weight (fp32 [B,H,W]) and disagree (uint8 [B,H,W]); each output may be None."""
+        self._have("pf_odo_fuse")
+        B, H, W = self._chk_odo_map(map_a, "odo_fuse: map_a")
+        if self._chk_odo_map(map_b, "odo_fuse: map_b") != (B, H, W):
+            raise PfError("odo_fuse: the two maps differ in shape")
+        dev = map_a[0].device
+        for name, x in (("S_a", S_a), ("S_b", S_b), ("link_valid", link_valid)):
+            self._chk_odo_vec(x, (B,), f"odo_fuse: {name}")
+        self._chk(inv_depth, weight)
+        for name, x in (("inv_depth", inv_depth), ("weight", weight)):
+            if x is not None and tuple(x.shape) != (B, H, W):
+                raise PfError(f"odo_fuse: {name} {tuple(x.shape)}, expected {(B, H, W)}")
+        self._chk_mask(disagree, (B, H, W), "odo_fuse: disagree")
+        if any(x is not None and x.device != dev for x in (map_b[0], S_a, S_b, link_valid, inv_depth, weight, disagree)):
+            raise PfError(f"odo_fuse: every tensor must be on {dev}")
+        self._rc(self._dll.pf_odo_fuse(_ptr(map_a[0]), _ptr(map_a[1]), _ptr(map_a[2]), _ptr(map_b[0]), _ptr(map_b[1]), _ptr(map_b[2]),
+                                       _ptr(S_a), _ptr(S_b), _ptr(link_valid), _ptr(inv_depth), _ptr(weight), _ptr(disagree), B, H, W,
+                                       float(conf_min), float(kappa_min), float(tol_log2), self._stream(map_a[0])), "pf_odo_fuse")
+        return inv_depth, weight, disagree
 
     # ---- self-supervised criterion (DESIGN.md section 21) --------------------------------------
     def selfsup_loss_batch(self, preds, image1, image2, weight, mask, i_weights, grads, partials, z: float, w_photo: float,
