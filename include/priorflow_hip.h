@@ -413,6 +413,46 @@ int pf_odo_fuse(const float* inv_a, const float* conf_a, const unsigned char* mo
                 const unsigned char* moving_b, const float* S_a, const float* S_b, const float* link_valid, float* inv_depth,
                 float* weight, unsigned char* disagree, int B, int H, int W, float conf_min, float kappa_min, float tol_log2, void* stream);
 
+/* Depth along the trajectory: rigid reprojection of an inverse-depth panorama into the next camera, a z-tested forward splat and a
+ * per-pixel recursive depth filter (the statement is prior-flow_amd/csrc/pf_reproject.h).  The convention
+ * is the block above's: a scene point X in the earlier frame's axes is R X + T in the later frame's; R [B,9] and T [B,3] fp32 in
+ * DEVICE memory, T in the unit of the inverse depth (T = baseline t).
+ *
+ * pf_reproj_project: per source pixel s = R p + d T, n = |s| (1 when T = 0), d' = d / n, flow = (ERP position of s) - (x, y), the
+ *   first component wrapped into [-W/2, W/2).  A pixel is left out (flow 0, d' 0, valid 0) when its mask byte is set (mask [B,H,W]
+ *   or NULL), !(weight > 0), !(0 <= d < 2^30) or !(n >= n_min).  flow [B,2,H,W], d_new [B,H,W], valid bytes [B,H,W].
+ * pf_zsplat_front / pf_zsplat_accumulate / pf_zsplat_resolve: the STORED flow, d, weight, valid and C = 0..4 payload planes src
+ *   [B,C,H,W] (NULL when C = 0) are splatted with pf_splat_accumulate's four taps (columns wrap, rows past a pole are dropped); a
+ *   pixel counts when valid != 0, weight > 0, 0 <= d < 2^30 and its landing point and payload values are below 2^30 in magnitude; a
+ *   tap is used when its bilinear weight b_k >= b_min.  front [B,H,W] uint32 (all-zero before the call) takes the maximum of the
+ *   bit patterns of d over the used taps; accumulate counts a tap iff d 2^tol_log2 >= front there and adds, as 64-bit integers
+ *   scaled by pf_splat_accumulate's rule for (1, H, W, max(dmax, vmax)), w_n b_k clamp(src_c, +-vmax), w_n b_k min(d, dmax), w_n b_k
+ *   and b_k into acc [B,C+3,H,W] int64 (pf_zsplat_bytes; all-zero before the call), w_n = min(weight, w_max) / w_max.  resolve: hole =
+ *   cov < cmin or D <= 0; d_out = N_d / D, w_out = w_max D / cov, out_c = N_c / D (out NULL when C = 0), a hole gives zeros and hole
+ *   byte 1; acc and front are written back as zeros.  No result depends on the order of the adds.
+ * pf_depth_update: the state (d_s, w_s) [B,H,W] in place from a measurement (d_m, w_m, disagree bytes or NULL), pf_odo_track's flags
+ *   [B,4] and the filter's seg [B] int32.  A side counts when its weight is positive and finite and 0 <= d < 2^30 (weights above
+ *   w_max are read as w_max); the state not in an image whose flags[1] != seg, the measurement not where disagree is set.  Both, within
+ *   |log2(d_m / d_s)| <= tol_log2: the mean weighted by decay w_s and w_m, w = min(decay w_s + w_m, w_max); both, further apart: the
+ *   measurement; one: that one (the state's weight decayed); neither: 0, 0.  A second launch then writes seg = flags[1].
+ * PF_ERR_BAD_ARG: a NULL input or required output, src / out given with C = 0 or missing with C > 0, C outside 0..4, a pointer not
+ * aligned to its element (acc: 8 bytes), an output, acc or front whose bytes meet an input's or another output's, n_min / w_max /
+ * cmin / tol_log2 of pf_depth_update not positive and finite, b_min outside [0, 1], tol_log2 of the splat outside [0, 64], decay
+ * outside (0, 1], dmax or vmax outside [1, 65536].  PF_ERR_BAD_SHAPE: B, H or W < 1, B > 65535, H * W >= 2^30.  Every refusal
+ * answers before anything is launched.  No host read, no allocation, capturable. */
+int pf_reproj_project(const float* inv_depth, const float* weight, const unsigned char* mask, const float* R, const float* T, float* flow,
+                      float* d_new, unsigned char* valid, int B, int H, int W, float n_min, void* stream);
+long pf_zsplat_bytes(int B, int C, int H, int W);
+int pf_zsplat_front(const float* src, const float* flow, const float* d, const float* weight, const unsigned char* valid, void* front,
+                    int B, int C, int H, int W, float b_min, void* stream);
+int pf_zsplat_accumulate(const float* src, const float* flow, const float* d, const float* weight, const unsigned char* valid,
+                         const void* front, void* acc, int B, int C, int H, int W, float b_min, float tol_log2, float w_max, float dmax,
+                         float vmax, void* stream);
+int pf_zsplat_resolve(void* acc, void* front, float* out, float* d_out, float* w_out, unsigned char* hole, int B, int C, int H, int W,
+                      float cmin, float w_max, float dmax, float vmax, void* stream);
+int pf_depth_update(float* d_s, float* w_s, const float* d_m, const float* w_m, const unsigned char* disagree, const int* flags, int* seg,
+                    int B, int H, int W, float tol_log2, float decay, float w_max, void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

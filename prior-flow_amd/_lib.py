@@ -198,17 +198,24 @@ _SIGNATURES = {
     "pf_odo_reverse_pose": [_fp, _fp, _fp, _fp, _i, _fp],
     "pf_odo_track": [_fp] * 10 + [_i, _fp],
     "pf_odo_fuse": [_fp] * 12 + [_i, _i, _i, C.c_float, C.c_float, C.c_float, _fp],
+    "pf_reproj_project": [_fp] * 8 + [_i, _i, _i, C.c_float, _fp],
+    "pf_zsplat_bytes": [_i, _i, _i, _i],
+    "pf_zsplat_front": [_fp] * 6 + [_i, _i, _i, _i, C.c_float, _fp],
+    "pf_zsplat_accumulate": [_fp] * 7 + [_i, _i, _i, _i] + [C.c_float] * 5 + [_fp],
+    "pf_zsplat_resolve": [_fp] * 6 + [_i, _i, _i, _i] + [C.c_float] * 4 + [_fp],
+    "pf_depth_update": [_fp] * 7 + [_i, _i, _i, C.c_float, C.c_float, C.c_float, _fp],
     "pf_selfsup_loss_batch": [_fp] * 8 + [_i] * 5 + [C.c_float] * 7 + [_i, _fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
 # entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp,
-# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp, pf_emu_odometry.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp, pf_emu_odometry.cpp, pf_emu_reproject.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
 _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert",
                   "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp",
                   "pf_splat_scratch_bytes", "pf_splat_accumulate", "pf_splat_resolve",
                   "pf_ego_scratch_bytes", "pf_ego_accumulate", "pf_ego_solve", "pf_ego_track", "pf_erp_rotate", "pf_ego_derotate",
                   "pf_epi_sums_bytes", "pf_epi_accumulate", "pf_epi_solve", "pf_epi_map", "pf_selfsup_loss_batch",
-                  "pf_odo_hist_bytes", "pf_odo_accumulate", "pf_odo_solve", "pf_odo_reverse_pose", "pf_odo_track", "pf_odo_fuse")
+                  "pf_odo_hist_bytes", "pf_odo_accumulate", "pf_odo_solve", "pf_odo_reverse_pose", "pf_odo_track", "pf_odo_fuse",
+                  "pf_reproj_project", "pf_zsplat_bytes", "pf_zsplat_front", "pf_zsplat_accumulate", "pf_zsplat_resolve", "pf_depth_update")
 EGO_SUMS, EGO_STATS, EGO_STATE = 12, 5, 8           # PF_EGO_SUMS, PF_EGO_STATS, PF_EGO_STATE
 EPI_SUMS, EPI_STATS = 22, 6                         # PF_EPI_SUMS, PF_EPI_STATS
 EPI_T, EPI_R = 0, 1                                 # PF_EPI_T / PF_EPI_R
@@ -299,7 +306,7 @@ class PfLib:
                     continue
                 raise PfError(f"{path} does not export {name}")
             fn.argtypes = args
-            fn.restype = C.c_long if name.endswith(("_ws_floats", "_scratch_bytes", "_sums_bytes", "_hist_bytes")) else _i
+            fn.restype = C.c_long if name.endswith(("_ws_floats", "_scratch_bytes", "_sums_bytes", "_hist_bytes", "_zsplat_bytes")) else _i
 
     # ---- helpers -----------------------------------------------------------------------------
     def version(self) -> str:
@@ -1531,6 +1538,137 @@ class PfLib:
                                        _ptr(S_a), _ptr(S_b), _ptr(link_valid), _ptr(inv_depth), _ptr(weight), _ptr(disagree), B, H, W,
                                        float(conf_min), float(kappa_min), float(tol_log2), self._stream(map_a[0])), "pf_odo_fuse")
         return inv_depth, weight, disagree
+
+    # ---- depth along the trajectory --------------------------------------
+    def zsplat_bytes(self, B: int, C_: int, H: int, W: int) -> int:
+        self._have("pf_zsplat_bytes")
+        r = self._dll.pf_zsplat_bytes(B, C_, H, W)
+        self._rc(min(r, 0), "pf_zsplat_bytes")
+        return r
+
+    def _chk_rp_maps(self, what, shape, dev, **maps):
+        """fp32 maps of one shape on one device (None allowed where the entry allows it)."""
+        self._chk(*maps.values())
+        for name, t in maps.items():
+            if t is not None and (tuple(t.shape) != tuple(shape) or t.device != dev):
+                raise PfError(f"{what}: {name} {tuple(t.shape)} on {t.device}, expected {tuple(shape)} on {dev}")
+
+    def _chk_rp_bytes(self, what, shape, dev, **maps):
+        for name, t in maps.items():
+            self._chk_mask(t, shape, f"{what}: {name}")
+            if t is not None and t.device != dev:
+                raise PfError(f"{what}: {name} must be on {dev}")
+
+    def reproj_project(self, inv_depth, weight, mask, R, T, flow, d_new, valid, n_min: float):
+        """pf_reproj_project: inv_depth, weight fp32 [B,H,W] (mask uint8 [B,H,W] or None) under R [B,3,3], T [B,3] into flow
+        [B,2,H,W], d_new [B,H,W] and valid uint8 [B,H,W]."""
+        self._have("pf_reproj_project")
+        self._chk(inv_depth)
+        if inv_depth.dim() != 3:
+            raise PfError(f"reproj_project: inv_depth {tuple(inv_depth.shape)}, expected [B,H,W]")
+        B, H, W = inv_depth.shape
+        dev = inv_depth.device
+        if weight is None or flow is None or d_new is None or valid is None or R is None or T is None:
+            raise PfError("reproj_project: only mask may be None")
+        self._chk_rp_maps("reproj_project", (B, H, W), dev, weight=weight, d_new=d_new)
+        self._chk_rp_maps("reproj_project", (B, 2, H, W), dev, flow=flow)
+        self._chk_rp_bytes("reproj_project", (B, H, W), dev, mask=mask, valid=valid)
+        self._chk_ego_mats(B, "reproj_project", R=R)
+        self._chk_epi_vecs(B, "reproj_project", T=T)
+        if R.device != dev or T.device != dev:
+            raise PfError(f"reproj_project: every tensor must be on {dev}")
+        self._rc(self._dll.pf_reproj_project(_ptr(inv_depth), _ptr(weight), _ptr(mask), _ptr(R), _ptr(T), _ptr(flow), _ptr(d_new),
+                                             _ptr(valid), B, H, W, float(n_min), self._stream(inv_depth)), "pf_reproj_project")
+        return flow, d_new, valid
+
+    def _chk_zsplat_in(self, what, src, flow, d, weight, valid, front):
+        self._chk(d)
+        if d.dim() != 3:
+            raise PfError(f"{what}: d {tuple(d.shape)}, expected [B,H,W]")
+        B, H, W = d.shape
+        dev = d.device
+        if flow is None or weight is None or valid is None or front is None:
+            raise PfError(f"{what}: only src may be None")
+        Cc = 0 if src is None else (src.shape[1] if src.dim() == 4 else -1)
+        if not 0 <= Cc <= 4 or (src is not None and Cc == 0):
+            raise PfError(f"{what}: src {tuple(src.shape)}, expected [B,C,H,W] with C = 1..4, or None")
+        self._chk_rp_maps(what, (B, H, W), dev, weight=weight)
+        self._chk_rp_maps(what, (B, 2, H, W), dev, flow=flow)
+        self._chk_rp_maps(what, (B, Cc, H, W), dev, src=src)
+        self._chk_rp_bytes(what, (B, H, W), dev, valid=valid)
+        self._chk_bytes(front, f"{what}: front", torch.int32)
+        if tuple(front.shape) != (B, H, W) or front.device != dev:
+            raise PfError(f"{what}: front {tuple(front.shape)}, expected int32 {(B, H, W)} on {dev}")
+        return B, Cc, H, W
+
+    def zsplat_front(self, src, flow, d, weight, valid, front, b_min: float):
+        """pf_zsplat_front: the nearest inverse depth that lands on each target, as bit patterns, into front int32 [B,H,W] (all-zero)."""
+        self._have("pf_zsplat_front")
+        B, Cc, H, W = self._chk_zsplat_in("zsplat_front", src, flow, d, weight, valid, front)
+        self._rc(self._dll.pf_zsplat_front(_ptr(src), _ptr(flow), _ptr(d), _ptr(weight), _ptr(valid), _ptr(front), B, Cc, H, W,
+                                           float(b_min), self._stream(d)), "pf_zsplat_front")
+
+    def _chk_zsplat_acc(self, what, acc, B, Cc, H, W, dev):
+        self._chk_bytes(acc, f"{what}: acc", torch.int64)
+        if tuple(acc.shape) != (B, Cc + 3, H, W) or acc.device != dev:
+            raise PfError(f"{what}: acc {tuple(acc.shape)}, expected int64 {(B, Cc + 3, H, W)} on {dev}")
+
+    def zsplat_accumulate(self, src, flow, d, weight, valid, front, acc, b_min: float, tol_log2: float, w_max: float, dmax: float,
+                          vmax: float):
+        """pf_zsplat_accumulate: the taps that pass the depth test against front into acc int64 [B,C+3,H,W] (all-zero)."""
+        self._have("pf_zsplat_accumulate")
+        B, Cc, H, W = self._chk_zsplat_in("zsplat_accumulate", src, flow, d, weight, valid, front)
+        self._chk_zsplat_acc("zsplat_accumulate", acc, B, Cc, H, W, d.device)
+        self._rc(self._dll.pf_zsplat_accumulate(_ptr(src), _ptr(flow), _ptr(d), _ptr(weight), _ptr(valid), _ptr(front), _ptr(acc), B, Cc,
+                                                H, W, float(b_min), float(tol_log2), float(w_max), float(dmax), float(vmax),
+                                                self._stream(d)), "pf_zsplat_accumulate")
+
+    def zsplat_resolve(self, acc, front, out, d_out, w_out, hole, cmin: float, w_max: float, dmax: float, vmax: float):
+        """pf_zsplat_resolve: out fp32 [B,C,H,W] (None when C = 0), d_out, w_out fp32 [B,H,W] and hole uint8 [B,H,W] from acc and
+        front, which are zeroed again; w_max, dmax, vmax: the accumulate call's."""
+        self._have("pf_zsplat_resolve")
+        self._chk(d_out)
+        if d_out.dim() != 3:
+            raise PfError(f"zsplat_resolve: d_out {tuple(d_out.shape)}, expected [B,H,W]")
+        B, H, W = d_out.shape
+        dev = d_out.device
+        if w_out is None or hole is None or front is None:
+            raise PfError("zsplat_resolve: only out may be None")
+        Cc = 0 if out is None else (out.shape[1] if out.dim() == 4 else -1)
+        if not 0 <= Cc <= 4 or (out is not None and Cc == 0):
+            raise PfError(f"zsplat_resolve: out {tuple(out.shape)}, expected [B,C,H,W] with C = 1..4, or None")
+        self._chk_rp_maps("zsplat_resolve", (B, H, W), dev, w_out=w_out)
+        self._chk_rp_maps("zsplat_resolve", (B, Cc, H, W), dev, out=out)
+        self._chk_rp_bytes("zsplat_resolve", (B, H, W), dev, hole=hole)
+        self._chk_bytes(front, "zsplat_resolve: front", torch.int32)
+        if tuple(front.shape) != (B, H, W) or front.device != dev:
+            raise PfError(f"zsplat_resolve: front {tuple(front.shape)}, expected int32 {(B, H, W)} on {dev}")
+        self._chk_zsplat_acc("zsplat_resolve", acc, B, Cc, H, W, dev)
+        self._rc(self._dll.pf_zsplat_resolve(_ptr(acc), _ptr(front), _ptr(out), _ptr(d_out), _ptr(w_out), _ptr(hole), B, Cc, H, W,
+                                             float(cmin), float(w_max), float(dmax), float(vmax), self._stream(d_out)),
+                 "pf_zsplat_resolve")
+        return out, d_out, w_out, hole
+
+    def depth_update(self, d_s, w_s, d_m, w_m, disagree, flags, seg, tol_log2: float, decay: float, w_max: float):
+        """pf_depth_update: the state (d_s, w_s) fp32 [B,H,W] in place from the measurement (d_m, w_m, disagree uint8 or None),
+        flags int32 [B,4] and seg int32 [B], which is rewritten after the pixel pass."""
+        self._have("pf_depth_update")
+        self._chk(d_s)
+        if d_s.dim() != 3:
+            raise PfError(f"depth_update: d_s {tuple(d_s.shape)}, expected [B,H,W]")
+        B, H, W = d_s.shape
+        dev = d_s.device
+        if w_s is None or d_m is None or w_m is None or flags is None or seg is None:
+            raise PfError("depth_update: only disagree may be None")
+        self._chk_rp_maps("depth_update", (B, H, W), dev, w_s=w_s, d_m=d_m, w_m=w_m)
+        self._chk_rp_bytes("depth_update", (B, H, W), dev, disagree=disagree)
+        self._chk_odo_vec(flags, (B, ODO_FLAGS), "depth_update: flags", torch.int32)
+        self._chk_odo_vec(seg, (B,), "depth_update: seg", torch.int32)
+        if flags.device != dev or seg.device != dev:
+            raise PfError(f"depth_update: every tensor must be on {dev}")
+        self._rc(self._dll.pf_depth_update(_ptr(d_s), _ptr(w_s), _ptr(d_m), _ptr(w_m), _ptr(disagree), _ptr(flags), _ptr(seg), B, H, W,
+                                           float(tol_log2), float(decay), float(w_max), self._stream(d_s)), "pf_depth_update")
+        return d_s, w_s
 
     # ---- self-supervised criterion (DESIGN.md section 21) --------------------------------------
     def selfsup_loss_batch(self, preds, image1, image2, weight, mask, i_weights, grads, partials, z: float, w_photo: float,
