@@ -453,6 +453,41 @@ int pf_zsplat_resolve(void* acc, void* front, float* out, float* d_out, float* w
 int pf_depth_update(float* d_s, float* w_s, const float* d_m, const float* w_m, const unsigned char* disagree, const int* flags, int* seg,
                     int B, int H, int W, float tol_log2, float decay, float w_max, void* stream);
 
+/* Moving objects: connected components of a byte mask on the cyclic panorama, per-component sums and a dense, capped object table
+ * (the statement is prior-flow_amd/csrc/pf_segments.h).
+ *
+ * pf_seg_tables: rows [H,2] = (cos phi, sin phi) of every row, cols [W,2] = (cos theta, sin theta) of every column, once per
+ *   geometry.  One launch.
+ * pf_seg_label: mask bytes [B,H,W] (a pixel is set when its byte is non-zero) into labels int32 [B,H,W]: 1 + the smallest linear
+ *   index y W + x of the pixel's component, 0 for background.  connectivity 4 or 8; column W-1 touches column 0 (at 8 also
+ *   diagonally); rows do not wrap; with poles = 1 the set pixels of row 0 are one component and so are those of row H-1.  The
+ *   labels are a function of the mask alone.  The area sums of the components (cos phi from rows, scaled by 2^32) are left in
+ *   scratch for pf_seg_objects.  Three launches.
+ * pf_seg_objects: the components of labels (as pf_seg_label left them, with the same scratch) whose area is at least min_area
+ *   (equatorial pixels) SURVIVE and are numbered 1, 2, ... by their smallest linear index.  ids int32 [B,H,W]: that number, 0 for
+ *   background, for a component that did not survive and for survivors beyond max_objects = M; keep bytes [B,H,W]: 1 on the pixels
+ *   of every survivor (those beyond M included); roots int32 [B,M]: the smallest linear index of each object, -1 where unused;
+ *   count int32 [B]: the number of survivors, NOT clipped to M; sums int64 [B,M,PF_SEG_SUMS]: area, pixels, cos phi * bearing (3),
+ *   value weight, cos phi * value (4) (scales 2^32, 1, 2^32, 2^32, 2^16); table fp32 [B,M,PF_SEG_COLS + C]: area, pixels, centroid
+ *   x, y in ERP pixels, resultant length, value weight, C value means; unused rows are zero.  values fp32 [B,C,H,W], C = 0..4 (NULL
+ *   when C = 0): a pixel's values count when every channel is below 2^16 in magnitude (a NaN does not).  Five launches.
+ * scratch: pf_seg_scratch_bytes(B, H, W) bytes, 8-byte aligned; its contents before a call do not matter.
+ * PF_ERR_BAD_ARG: a NULL where one is required, values given with C = 0 or missing with C > 0, C outside 0..4, connectivity not 4
+ * or 8, poles not 0 or 1, max_objects outside 1..PF_SEG_MAX_OBJECTS, min_area negative, above 2^30 or NaN, a pointer not aligned
+ * to its element (scratch, sums: 8 bytes), scratch_bytes too small, an output or scratch whose bytes meet an input's or another
+ * output's.  PF_ERR_BAD_SHAPE: B, H or W < 1, B > 65535, H * W >= 2^30 (beyond which the 64-bit sums could not hold).  Every
+ * refusal answers before anything is launched.  No host read, no allocation, capturable. */
+#define PF_SEG_SUMS 10
+#define PF_SEG_COLS 6
+#define PF_SEG_MAX_OBJECTS 4096
+long pf_seg_scratch_bytes(int B, int H, int W);
+int pf_seg_tables(float* rows, float* cols, int H, int W, void* stream);
+int pf_seg_label(const unsigned char* mask, const float* rows, int* labels, void* scratch, long scratch_bytes, int B, int H, int W,
+                 int connectivity, int poles, void* stream);
+int pf_seg_objects(const int* labels, const float* values, const float* rows, const float* cols, void* scratch, long scratch_bytes,
+                   int* ids, unsigned char* keep, int* roots, int* count, float* table, void* sums, int B, int C, int H, int W,
+                   int max_objects, float min_area, void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

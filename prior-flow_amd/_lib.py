@@ -205,21 +205,27 @@ _SIGNATURES = {
     "pf_zsplat_resolve": [_fp] * 6 + [_i, _i, _i, _i] + [C.c_float] * 4 + [_fp],
     "pf_depth_update": [_fp] * 7 + [_i, _i, _i, C.c_float, C.c_float, C.c_float, _fp],
     "pf_selfsup_loss_batch": [_fp] * 8 + [_i] * 5 + [C.c_float] * 7 + [_i, _fp],
+    "pf_seg_scratch_bytes": [_i, _i, _i],
+    "pf_seg_tables": [_fp, _fp, _i, _i, _fp],
+    "pf_seg_label": [_fp, _fp, _fp, _fp, C.c_long, _i, _i, _i, _i, _i, _fp],
+    "pf_seg_objects": [_fp] * 5 + [C.c_long] + [_fp] * 6 + [_i] * 5 + [C.c_float, _fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
 # entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp,
-# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp, pf_emu_odometry.cpp, pf_emu_reproject.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp, pf_emu_odometry.cpp, pf_emu_reproject.cpp, pf_emu_segments.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
 _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert",
                   "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp",
                   "pf_splat_scratch_bytes", "pf_splat_accumulate", "pf_splat_resolve",
                   "pf_ego_scratch_bytes", "pf_ego_accumulate", "pf_ego_solve", "pf_ego_track", "pf_erp_rotate", "pf_ego_derotate",
                   "pf_epi_sums_bytes", "pf_epi_accumulate", "pf_epi_solve", "pf_epi_map", "pf_selfsup_loss_batch",
                   "pf_odo_hist_bytes", "pf_odo_accumulate", "pf_odo_solve", "pf_odo_reverse_pose", "pf_odo_track", "pf_odo_fuse",
-                  "pf_reproj_project", "pf_zsplat_bytes", "pf_zsplat_front", "pf_zsplat_accumulate", "pf_zsplat_resolve", "pf_depth_update")
+                  "pf_reproj_project", "pf_zsplat_bytes", "pf_zsplat_front", "pf_zsplat_accumulate", "pf_zsplat_resolve", "pf_depth_update",
+                  "pf_seg_scratch_bytes", "pf_seg_tables", "pf_seg_label", "pf_seg_objects")
 EGO_SUMS, EGO_STATS, EGO_STATE = 12, 5, 8           # PF_EGO_SUMS, PF_EGO_STATS, PF_EGO_STATE
 EPI_SUMS, EPI_STATS = 22, 6                         # PF_EPI_SUMS, PF_EPI_STATS
 EPI_T, EPI_R = 0, 1                                 # PF_EPI_T / PF_EPI_R
 ODO_STATS, ODO_STATE, ODO_FLAGS = 6, 12, 4          # PF_ODO_STATS, PF_ODO_STATE, PF_ODO_FLAGS
+SEG_SUMS, SEG_COLS, SEG_MAX_OBJECTS = 10, 6, 4096   # PF_SEG_SUMS, PF_SEG_COLS, PF_SEG_MAX_OBJECTS
 SS_MAX, SS_SUMS = 32, 4                             # PF_SS_MAX, PF_SS_SUMS
 SPLAT_MAX = 4                                       # PF_SPLAT_MAX
 AUG_ROW_WORDS = 32                                  # PF_AUG_ROW_WORDS
@@ -1669,6 +1675,78 @@ class PfLib:
         self._rc(self._dll.pf_depth_update(_ptr(d_s), _ptr(w_s), _ptr(d_m), _ptr(w_m), _ptr(disagree), _ptr(flags), _ptr(seg), B, H, W,
                                            float(tol_log2), float(decay), float(w_max), self._stream(d_s)), "pf_depth_update")
         return d_s, w_s
+
+    # ---- moving objects -------------------------------------------------
+    def seg_scratch_bytes(self, B: int, H: int, W: int) -> int:
+        self._have("pf_seg_scratch_bytes")
+        r = self._dll.pf_seg_scratch_bytes(B, H, W)
+        self._rc(min(r, 0), "pf_seg_scratch_bytes")
+        return r
+
+    def seg_tables(self, rows, cols):
+        """pf_seg_tables: rows fp32 [H,2] = (cos phi, sin phi), cols fp32 [W,2] = (cos theta, sin theta)."""
+        self._have("pf_seg_tables")
+        self._chk(rows, cols)
+        if rows.dim() != 2 or cols.dim() != 2 or rows.shape[1] != 2 or cols.shape[1] != 2 or rows.device != cols.device:
+            raise PfError(f"seg_tables: rows {tuple(rows.shape)}, cols {tuple(cols.shape)}, expected [H,2] and [W,2] on one device")
+        self._rc(self._dll.pf_seg_tables(_ptr(rows), _ptr(cols), rows.shape[0], cols.shape[0], self._stream(rows)), "pf_seg_tables")
+        return rows, cols
+
+    def _chk_seg_scratch(self, what, scratch, dev):
+        self._chk_bytes(scratch, f"{what}: scratch")
+        if scratch.device != dev:
+            raise PfError(f"{what}: scratch must be on {dev}")
+        return scratch.numel() * scratch.element_size()
+
+    def seg_label(self, mask, rows, labels, scratch, connectivity: int, poles: bool):
+        """pf_seg_label: mask uint8 [B,H,W] into labels int32 [B,H,W] (1 + the smallest linear index of the component, 0 for
+        background); rows: seg_tables' [H,2]; scratch: seg_scratch_bytes."""
+        self._have("pf_seg_label")
+        if mask.dim() != 3:
+            raise PfError(f"seg_label: mask {tuple(mask.shape)}, expected [B,H,W]")
+        B, H, W = mask.shape
+        dev = mask.device
+        self._chk_rp_bytes("seg_label", (B, H, W), dev, mask=mask)
+        self._chk_rp_maps("seg_label", (H, 2), dev, rows=rows)
+        self._chk_odo_vec(labels, (B, H, W), "seg_label: labels", torch.int32)
+        if labels.device != dev or rows is None:
+            raise PfError(f"seg_label: every tensor must be on {dev}")
+        nbytes = self._chk_seg_scratch("seg_label", scratch, dev)
+        self._rc(self._dll.pf_seg_label(_ptr(mask), _ptr(rows), _ptr(labels), _ptr(scratch), nbytes, B, H, W, int(connectivity),
+                                        int(poles), self._stream(mask)), "pf_seg_label")
+        return labels
+
+    def seg_objects(self, labels, values, rows, cols, scratch, ids, keep, roots, count, table, sums, min_area: float):
+        """pf_seg_objects: the components of labels int32 [B,H,W] (and scratch, as seg_label left them) into ids int32 [B,H,W],
+        keep uint8 [B,H,W], roots int32 [B,M], count int32 [B], table fp32 [B,M,SEG_COLS + C] and sums int64 [B,M,SEG_SUMS];
+        values fp32 [B,C,H,W] or None."""
+        self._have("pf_seg_objects")
+        if labels.dim() != 3 or roots.dim() != 2:
+            raise PfError(f"seg_objects: labels {tuple(labels.shape)}, roots {tuple(roots.shape)}, expected [B,H,W] and [B,M]")
+        B, H, W = labels.shape
+        M = roots.shape[1]
+        dev = labels.device
+        Cc = 0 if values is None else (values.shape[1] if values.dim() == 4 else -1)
+        if not 0 <= Cc <= 4 or (values is not None and Cc == 0):
+            raise PfError(f"seg_objects: values {tuple(values.shape)}, expected [B,C,H,W] with C = 1..4, or None")
+        self._chk_rp_maps("seg_objects", (B, Cc, H, W), dev, values=values)
+        self._chk_rp_maps("seg_objects", (H, 2), dev, rows=rows)
+        self._chk_rp_maps("seg_objects", (W, 2), dev, cols=cols)
+        self._chk_rp_maps("seg_objects", (B, M, SEG_COLS + Cc), dev, table=table)
+        self._chk_rp_bytes("seg_objects", (B, H, W), dev, keep=keep)
+        for t, shape, what, dt in ((labels, (B, H, W), "labels", torch.int32), (ids, (B, H, W), "ids", torch.int32),
+                                   (roots, (B, M), "roots", torch.int32), (count, (B,), "count", torch.int32),
+                                   (sums, (B, M, SEG_SUMS), "sums", torch.int64)):
+            self._chk_odo_vec(t, shape, f"seg_objects: {what}", dt)
+            if t.device != dev:
+                raise PfError(f"seg_objects: {what} must be on {dev}")
+        if rows is None or cols is None or table is None or keep is None:
+            raise PfError("seg_objects: only values may be None")
+        nbytes = self._chk_seg_scratch("seg_objects", scratch, dev)
+        self._rc(self._dll.pf_seg_objects(_ptr(labels), _ptr(values), _ptr(rows), _ptr(cols), _ptr(scratch), nbytes, _ptr(ids),
+                                          _ptr(keep), _ptr(roots), _ptr(count), _ptr(table), _ptr(sums), B, Cc, H, W, M, float(min_area),
+                                          self._stream(labels)), "pf_seg_objects")
+        return ids, count, table
 
     # ---- self-supervised criterion (DESIGN.md section 21) --------------------------------------
     def selfsup_loss_batch(self, preds, image1, image2, weight, mask, i_weights, grads, partials, z: float, w_photo: float,
