@@ -488,6 +488,37 @@ int pf_seg_objects(const int* labels, const float* values, const float* rows, co
                    int* ids, unsigned char* keep, int* roots, int* count, float* table, void* sums, int B, int C, int H, int W,
                    int max_objects, float min_area, void* stream);
 
+/* Object tracks: persistent ids for the objects of pf_seg_objects across frames, from flow votes (the
+ * statement is prior-flow_amd/csrc/pf_tracker.h).  A push is pf_trk_begin, pf_trk_vote, pf_trk_match, pf_trk_paint: four launches
+ * with one flow, five with two.
+ *
+ * pf_trk_begin: clears votes int64 [B,M,M].
+ * pf_trk_vote: every pixel of prev_ids with an id in 1..M follows flow_prev (fp32 [B,2,H,W], on the previous grid, pointing into
+ *   the current frame) to the nearest pixel (x cyclic), every pixel of ids follows flow_cur (on the current grid, pointing into
+ *   the previous frame); where the target holds an id of the other map the pixel adds its area weight (cos phi of its row from
+ *   rows, scaled by 2^32) to votes[prev id - 1][cur id - 1].  Either flow may be NULL, not both.  mask_prev, mask_cur: bytes
+ *   [B,H,W] or NULL; a pixel with a non-zero byte, with |u| or |v| not below 2^30 or with a target row outside the image does not
+ *   vote.  One launch per flow.
+ * pf_trk_match: admissible cells (at least min_overlap * n_dir * the smaller of the two areas, and at least 1), mutual best match
+ *   with ties to the smallest index, then per current slot track, age, origin int32 [B,M], step, path fp32 [B,M] and per previous
+ *   slot fate int32 [B,M].  count, sums: pf_seg_objects' of the current frame.  The state (st_count [B], st_sums
+ *   [B,M,PF_SEG_SUMS], st_track, st_age, st_path [B,M], next_id [B]) is the previous frame's on entry and the current frame's on
+ *   return; all of it is read before any of it is written.  A state of zeros with next_id = 1 is the empty one.  n_dir: the number
+ *   of flows that voted, 1 or 2.  One launch, one workgroup per image.
+ * pf_trk_paint: track_map int32 [B,H,W] = the track of each pixel's object, 0 where ids is 0; st_ids = ids.  One launch.
+ * PF_ERR_BAD_ARG: a NULL where a pointer is required or both flows NULL, min_overlap outside (0, 1] or NaN, n_dir not 1 or 2, a
+ * pointer not aligned to its element (votes, sums: 8 bytes), an output or a state whose bytes meet an input's or another output's.
+ * PF_ERR_BAD_SHAPE: B, H or W < 1, B > 65535, H * W >= 2^30, M outside 1..PF_TRK_MAX_OBJECTS.  Every refusal answers before
+ * anything is launched.  No host read, no allocation, capturable. */
+#define PF_TRK_MAX_OBJECTS 256
+int pf_trk_begin(void* votes, int B, int M, void* stream);
+int pf_trk_vote(const int* prev_ids, const int* ids, const float* flow_prev, const float* flow_cur, const unsigned char* mask_prev,
+                const unsigned char* mask_cur, const float* rows, void* votes, int B, int H, int W, int M, void* stream);
+int pf_trk_match(const void* votes, const int* count, const void* sums, int* st_count, void* st_sums, int* st_track, int* st_age,
+                 float* st_path, int* next_id, int* track, int* age, int* origin, int* fate, float* step, float* path, int B, int M,
+                 int n_dir, float min_overlap, void* stream);
+int pf_trk_paint(const int* ids, const int* track, int* track_map, int* st_ids, int B, int H, int W, int M, void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

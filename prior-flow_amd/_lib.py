@@ -209,10 +209,14 @@ _SIGNATURES = {
     "pf_seg_tables": [_fp, _fp, _i, _i, _fp],
     "pf_seg_label": [_fp, _fp, _fp, _fp, C.c_long, _i, _i, _i, _i, _i, _fp],
     "pf_seg_objects": [_fp] * 5 + [C.c_long] + [_fp] * 6 + [_i] * 5 + [C.c_float, _fp],
+    "pf_trk_begin": [_fp, _i, _i, _fp],
+    "pf_trk_vote": [_fp] * 8 + [_i] * 4 + [_fp],
+    "pf_trk_match": [_fp] * 15 + [_i] * 3 + [C.c_float, _fp],
+    "pf_trk_paint": [_fp] * 4 + [_i] * 4 + [_fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
 # entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp,
-# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp, pf_emu_odometry.cpp, pf_emu_reproject.cpp, pf_emu_segments.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp, pf_emu_odometry.cpp, pf_emu_reproject.cpp, pf_emu_segments.cpp, pf_emu_tracker.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
 _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert",
                   "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp",
                   "pf_splat_scratch_bytes", "pf_splat_accumulate", "pf_splat_resolve",
@@ -220,12 +224,14 @@ _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_conv
                   "pf_epi_sums_bytes", "pf_epi_accumulate", "pf_epi_solve", "pf_epi_map", "pf_selfsup_loss_batch",
                   "pf_odo_hist_bytes", "pf_odo_accumulate", "pf_odo_solve", "pf_odo_reverse_pose", "pf_odo_track", "pf_odo_fuse",
                   "pf_reproj_project", "pf_zsplat_bytes", "pf_zsplat_front", "pf_zsplat_accumulate", "pf_zsplat_resolve", "pf_depth_update",
-                  "pf_seg_scratch_bytes", "pf_seg_tables", "pf_seg_label", "pf_seg_objects")
+                  "pf_seg_scratch_bytes", "pf_seg_tables", "pf_seg_label", "pf_seg_objects",
+                  "pf_trk_begin", "pf_trk_vote", "pf_trk_match", "pf_trk_paint")
 EGO_SUMS, EGO_STATS, EGO_STATE = 12, 5, 8           # PF_EGO_SUMS, PF_EGO_STATS, PF_EGO_STATE
 EPI_SUMS, EPI_STATS = 22, 6                         # PF_EPI_SUMS, PF_EPI_STATS
 EPI_T, EPI_R = 0, 1                                 # PF_EPI_T / PF_EPI_R
 ODO_STATS, ODO_STATE, ODO_FLAGS = 6, 12, 4          # PF_ODO_STATS, PF_ODO_STATE, PF_ODO_FLAGS
 SEG_SUMS, SEG_COLS, SEG_MAX_OBJECTS = 10, 6, 4096   # PF_SEG_SUMS, PF_SEG_COLS, PF_SEG_MAX_OBJECTS
+TRK_MAX_OBJECTS = 256                               # PF_TRK_MAX_OBJECTS
 SS_MAX, SS_SUMS = 32, 4                             # PF_SS_MAX, PF_SS_SUMS
 SPLAT_MAX = 4                                       # PF_SPLAT_MAX
 AUG_ROW_WORDS = 32                                  # PF_AUG_ROW_WORDS
@@ -1747,6 +1753,83 @@ class PfLib:
                                           _ptr(keep), _ptr(roots), _ptr(count), _ptr(table), _ptr(sums), B, Cc, H, W, M, float(min_area),
                                           self._stream(labels)), "pf_seg_objects")
         return ids, count, table
+
+    # ---- object tracks ---------------------------------------------------
+    def _chk_trk(self, what, dev, specs):
+        """specs: (tensor, shape, name, dtype); every one a contiguous tensor of that dtype and shape on dev."""
+        for t, shape, name, dt in specs:
+            if t is None:
+                raise PfError(f"{what}: {name} is required")
+            self._chk_odo_vec(t, shape, f"{what}: {name}", dt)
+            if t.device != dev:
+                raise PfError(f"{what}: {name} must be on {dev}")
+
+    def trk_begin(self, votes):
+        """pf_trk_begin: clears votes int64 [B,M,M]."""
+        self._have("pf_trk_begin")
+        if votes.dim() != 3 or votes.shape[1] != votes.shape[2]:
+            raise PfError(f"trk_begin: votes {tuple(votes.shape)}, expected [B,M,M]")
+        self._chk_odo_vec(votes, tuple(votes.shape), "trk_begin: votes", torch.int64)
+        self._rc(self._dll.pf_trk_begin(_ptr(votes), votes.shape[0], votes.shape[1], self._stream(votes)), "pf_trk_begin")
+        return votes
+
+    def trk_vote(self, prev_ids, ids, flow_prev, flow_cur, mask_prev, mask_cur, rows, votes):
+        """pf_trk_vote: the pixels of prev_ids int32 [B,H,W] along flow_prev and those of ids along flow_cur (fp32 [B,2,H,W]; one may
+        be None) into votes int64 [B,M,M]; mask_prev, mask_cur uint8 [B,H,W] or None; rows: seg_tables' [H,2]."""
+        self._have("pf_trk_vote")
+        if prev_ids.dim() != 3 or votes.dim() != 3 or votes.shape[1] != votes.shape[2]:
+            raise PfError(f"trk_vote: prev_ids {tuple(prev_ids.shape)}, votes {tuple(votes.shape)}, expected [B,H,W] and [B,M,M]")
+        B, H, W = prev_ids.shape
+        M = votes.shape[1]
+        dev = prev_ids.device
+        if flow_prev is None and flow_cur is None:
+            raise PfError("trk_vote: at least one flow is required")
+        self._chk_trk("trk_vote", dev, ((prev_ids, (B, H, W), "prev_ids", torch.int32), (ids, (B, H, W), "ids", torch.int32),
+                                        (votes, (B, M, M), "votes", torch.int64)))
+        self._chk_rp_maps("trk_vote", (B, 2, H, W), dev, flow_prev=flow_prev, flow_cur=flow_cur)
+        self._chk_rp_maps("trk_vote", (H, 2), dev, rows=rows)
+        self._chk_rp_bytes("trk_vote", (B, H, W), dev, mask_prev=mask_prev, mask_cur=mask_cur)
+        if rows is None:
+            raise PfError("trk_vote: rows is required")
+        self._rc(self._dll.pf_trk_vote(_ptr(prev_ids), _ptr(ids), _ptr(flow_prev), _ptr(flow_cur), _ptr(mask_prev), _ptr(mask_cur),
+                                       _ptr(rows), _ptr(votes), B, H, W, M, self._stream(prev_ids)), "pf_trk_vote")
+        return votes
+
+    def trk_match(self, votes, count, sums, st_count, st_sums, st_track, st_age, st_path, next_id, track, age, origin, fate, step, path,
+                  n_dir: int, min_overlap: float):
+        """pf_trk_match: votes int64 [B,M,M] and the current count int32 [B], sums int64 [B,M,SEG_SUMS] against the state (st_count
+        [B], st_sums [B,M,SEG_SUMS], st_track, st_age int32 [B,M], st_path fp32 [B,M], next_id int32 [B]; updated in place) into
+        track, age, origin, fate int32 [B,M] and step, path fp32 [B,M]."""
+        self._have("pf_trk_match")
+        if votes.dim() != 3 or votes.shape[1] != votes.shape[2]:
+            raise PfError(f"trk_match: votes {tuple(votes.shape)}, expected [B,M,M]")
+        B, M = votes.shape[:2]
+        dev = votes.device
+        i32, i64, f32 = torch.int32, torch.int64, torch.float32
+        self._chk_trk("trk_match", dev, (
+            (votes, (B, M, M), "votes", i64), (count, (B,), "count", i32), (sums, (B, M, SEG_SUMS), "sums", i64),
+            (st_count, (B,), "st_count", i32), (st_sums, (B, M, SEG_SUMS), "st_sums", i64), (st_track, (B, M), "st_track", i32),
+            (st_age, (B, M), "st_age", i32), (st_path, (B, M), "st_path", f32), (next_id, (B,), "next_id", i32),
+            (track, (B, M), "track", i32), (age, (B, M), "age", i32), (origin, (B, M), "origin", i32), (fate, (B, M), "fate", i32),
+            (step, (B, M), "step", f32), (path, (B, M), "path", f32)))
+        self._rc(self._dll.pf_trk_match(_ptr(votes), _ptr(count), _ptr(sums), _ptr(st_count), _ptr(st_sums), _ptr(st_track), _ptr(st_age),
+                                        _ptr(st_path), _ptr(next_id), _ptr(track), _ptr(age), _ptr(origin), _ptr(fate), _ptr(step),
+                                        _ptr(path), B, M, int(n_dir), float(min_overlap), self._stream(votes)), "pf_trk_match")
+        return track, age
+
+    def trk_paint(self, ids, track, track_map, st_ids):
+        """pf_trk_paint: track_map int32 [B,H,W] = track int32 [B,M] of each pixel's id (0 where ids is 0); st_ids = ids."""
+        self._have("pf_trk_paint")
+        if ids.dim() != 3 or track.dim() != 2:
+            raise PfError(f"trk_paint: ids {tuple(ids.shape)}, track {tuple(track.shape)}, expected [B,H,W] and [B,M]")
+        B, H, W = ids.shape
+        M = track.shape[1]
+        i32 = torch.int32
+        self._chk_trk("trk_paint", ids.device, ((ids, (B, H, W), "ids", i32), (track, (B, M), "track", i32),
+                                                (track_map, (B, H, W), "track_map", i32), (st_ids, (B, H, W), "st_ids", i32)))
+        self._rc(self._dll.pf_trk_paint(_ptr(ids), _ptr(track), _ptr(track_map), _ptr(st_ids), B, H, W, M, self._stream(ids)),
+                 "pf_trk_paint")
+        return track_map
 
     # ---- self-supervised criterion (DESIGN.md section 21) --------------------------------------
     def selfsup_loss_batch(self, preds, image1, image2, weight, mask, i_weights, grads, partials, z: float, w_photo: float,
