@@ -116,9 +116,9 @@ def _validation(dll):
     odd = ctypes.c_void_p(f.data_ptr() + 4)                 # not 16-byte aligned
     ok = dict(B=1, H8=16, W8=32, C=256, ld=324)
 
-    def look(coords=p, f1=p, own=p, raw=ctypes.c_void_p(f.data_ptr() + 64), **kw):
+    def look(coords=p, f1=p, own=p, raw=ctypes.c_void_p(f.data_ptr() + 64), own_l2=p, oth_l3=p, **kw):
         a = dict(ok, **kw)
-        return dll.pf_dccl_lookup_feat(coords, f1, p, p, p, p, p, p, p, p, p, p, own, raw, None,
+        return dll.pf_dccl_lookup_feat(coords, f1, p, p, own_l2, p, p, p, p, p, oth_l3, p, own, raw, None,
                                        a["B"], a["H8"], a["W8"], a["C"], a["ld"], None)
     assert look(coords=None) == -1                          # PF_ERR_BAD_ARG
     assert look(f1=None) == -1
@@ -131,6 +131,9 @@ def _validation(dll):
     assert look(H8=15) == -2                                # level 3 would be 1 x 4
     assert look(W8=8) == -2
     assert look(B=0) == -2
+    assert look(C=516) == -2                                # one float4 past the two channel groups a lane holds
+    assert look(own_l2=odd) == -1 and look(oth_l3=odd) == -1        # a misaligned pooled level of either view
+    assert look(own_l2=None) == -1 and look(oth_l3=None) == -1
 
     def pyr(f2=p, l1=p, **kw):
         a = dict(ok, **kw)
