@@ -519,6 +519,41 @@ int pf_trk_match(const void* votes, const int* count, const void* sums, int* st_
                  int n_dir, float min_overlap, void* stream);
 int pf_trk_paint(const int* ids, const int* track, int* track_map, int* st_ids, int B, int H, int W, int M, void* stream);
 
+/* Push-pull hole filling on the cyclic panorama (the statement is prior-flow_amd/csrc/pf_fill.h): a weighted
+ * pyramid of what is known (pull, 2 x 2 blocks, no wrap), expanded back (push, bilinear, columns wrapped, rows clamped) and taken
+ * only where the finer level knows nothing.  Gather only: the same bits on every run.
+ *
+ * src fp32 [B,C,H,W], C = 1..4; hole uint8 [B,H,W], non-zero: missing; weight fp32 [B,H,W] or NULL: a soft weight, cut to [0, 1].
+ * A pixel whose values are not finite (or at or beyond 2^30 in magnitude) or whose weight is not finite or <= 0 counts as a hole.
+ * pf_fill_levels: the number of pulls L until the level is 1 x 1 (H_(l+1) = max(1, ceil(H_l / 2))), or PF_ERR_BAD_SHAPE.
+ * pf_fill_bytes: the bytes of scratch for the shape (w0 [B,H,W], then per level l = 1..L the values [B,C,H_l,W_l] and the weights
+ *   [B,H_l,W_l], all fp32), or a negative PF_ERR_* code.  scratch needs no initialisation and is private to a call until it ends.
+ * pf_fill_pushpull: out fp32 [B,C,H,W] = src with its holes closed (a valid pixel of weight 1 keeps its bits), empty uint8 [B] or
+ *   NULL = 1 where an image has nothing valid (its out is 0).  Three launches when the levels above the fifth fit the apex kernel's
+ *   LDS (about 600 000 pixels at C = 4), two more per level beyond.  out may be exactly src.
+ * The level-by-level form, one launch each, the same bits: pf_fill_prepare writes w0 [B,H,W]; pf_fill_pull_level the level above
+ *   (coarse_v [B,C,Hc,Wc], coarse_w [B,Hc,Wc], Hc = max(1, ceil(Hf / 2))) of (fine_v [B,C,Hf,Wf], fine_w [B,Hf,Wf]);
+ *   pf_fill_push_level out [B,C,Hf,Wf] from the filled level above coarse_u [B,C,Hc,Wc]; out may be exactly fine_v.  At the 1 x 1
+ *   level coarse_u is NULL: the apex step, which alone may write empty.
+ * PF_ERR_BAD_ARG: a NULL where a pointer is required, a float map not aligned to 4 bytes, C outside 1..4, an output or scratch whose
+ * bytes meet an input's or another output's (other than out == src / out == fine_v), coarse_u given at the 1 x 1 level or missing
+ * elsewhere, empty given elsewhere.  PF_ERR_BAD_SHAPE: B, H or W < 1, B > 65535, H * W >= 2^30, a pull of the 1 x 1 level.  Every
+ * refusal answers before anything is launched.  No atomics, no memset, no host read, no allocation, capturable. */
+int pf_fill_levels(int H, int W);
+long pf_fill_bytes(int B, int C, int H, int W);
+int pf_fill_pushpull(const float* src, const unsigned char* hole, const float* weight, float* out, unsigned char* empty, void* scratch,
+                     int B, int C, int H, int W, void* stream);
+/* One stage of pf_fill_pushpull alone, on a scratch that a whole call has filled: 0 the pull tiles, 1 the apex kernel (with the
+ * level-by-level launches around it on a large map), 2 the push tiles.  For timing (profiles/time_fill.py) and for a test of the
+ * split: the three stages in order are pf_fill_pushpull.  PF_ERR_BAD_ARG: another stage. */
+int pf_fill_stage(const float* src, const unsigned char* hole, const float* weight, float* out, unsigned char* empty, void* scratch,
+                  int B, int C, int H, int W, int stage, void* stream);
+int pf_fill_prepare(const float* src, const unsigned char* hole, const float* weight, float* w0, int B, int C, int H, int W, void* stream);
+int pf_fill_pull_level(const float* fine_v, const float* fine_w, float* coarse_v, float* coarse_w, int B, int C, int Hf, int Wf,
+                       void* stream);
+int pf_fill_push_level(const float* coarse_u, const float* fine_v, const float* fine_w, float* out, unsigned char* empty, int B, int C,
+                       int Hf, int Wf, void* stream);
+
 /* flow = coords1 - coords_grid (core/prior_raft.py:172,177).  coords1: planar.  flow_out
  * (planar) and the two channel-last destinations are optional (NULL to skip). */
 int pf_flow_prep(const float* coords1, float* flow_out,

@@ -213,10 +213,17 @@ _SIGNATURES = {
     "pf_trk_vote": [_fp] * 8 + [_i] * 4 + [_fp],
     "pf_trk_match": [_fp] * 15 + [_i] * 3 + [C.c_float, _fp],
     "pf_trk_paint": [_fp] * 4 + [_i] * 4 + [_fp],
+    "pf_fill_levels": [_i, _i],
+    "pf_fill_bytes": [_i, _i, _i, _i],
+    "pf_fill_pushpull": [_fp] * 6 + [_i] * 4 + [_fp],
+    "pf_fill_stage": [_fp] * 6 + [_i] * 5 + [_fp],
+    "pf_fill_prepare": [_fp] * 4 + [_i] * 4 + [_fp],
+    "pf_fill_pull_level": [_fp] * 4 + [_i] * 4 + [_fp],
+    "pf_fill_push_level": [_fp] * 5 + [_i] * 4 + [_fp],
 }
 EXPORTS = ["pf_version"] + list(_SIGNATURES)
 # entry points whose host emulation is a library of its own (tests/emu/pf_emu_augment.cpp, pf_emu_viewport.cpp,
-# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp, pf_emu_odometry.cpp, pf_emu_reproject.cpp, pf_emu_segments.cpp, pf_emu_tracker.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
+# pf_emu_splat.cpp, pf_emu_egomotion.cpp, pf_emu_epipolar.cpp, pf_emu_selfsup.cpp, pf_emu_odometry.cpp, pf_emu_reproject.cpp, pf_emu_segments.cpp, pf_emu_tracker.cpp, pf_emu_fill.cpp): a host-only handle (require_cuda=False) may lack them and then refuses the call; the product's handle never may
 _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_convert",
                   "pf_viewport_image", "pf_viewport_flow", "pf_cubemap_to_erp",
                   "pf_splat_scratch_bytes", "pf_splat_accumulate", "pf_splat_resolve",
@@ -225,7 +232,9 @@ _OWN_EMULATION = ("pf_augment_scratch_bytes", "pf_augment_360", "pf_augment_conv
                   "pf_odo_hist_bytes", "pf_odo_accumulate", "pf_odo_solve", "pf_odo_reverse_pose", "pf_odo_track", "pf_odo_fuse",
                   "pf_reproj_project", "pf_zsplat_bytes", "pf_zsplat_front", "pf_zsplat_accumulate", "pf_zsplat_resolve", "pf_depth_update",
                   "pf_seg_scratch_bytes", "pf_seg_tables", "pf_seg_label", "pf_seg_objects",
-                  "pf_trk_begin", "pf_trk_vote", "pf_trk_match", "pf_trk_paint")
+                  "pf_trk_begin", "pf_trk_vote", "pf_trk_match", "pf_trk_paint",
+                  "pf_fill_levels", "pf_fill_bytes", "pf_fill_pushpull", "pf_fill_stage", "pf_fill_prepare", "pf_fill_pull_level",
+                  "pf_fill_push_level")
 EGO_SUMS, EGO_STATS, EGO_STATE = 12, 5, 8           # PF_EGO_SUMS, PF_EGO_STATS, PF_EGO_STATE
 EPI_SUMS, EPI_STATS = 22, 6                         # PF_EPI_SUMS, PF_EPI_STATS
 EPI_T, EPI_R = 0, 1                                 # PF_EPI_T / PF_EPI_R
@@ -318,7 +327,7 @@ class PfLib:
                     continue
                 raise PfError(f"{path} does not export {name}")
             fn.argtypes = args
-            fn.restype = C.c_long if name.endswith(("_ws_floats", "_scratch_bytes", "_sums_bytes", "_hist_bytes", "_zsplat_bytes")) else _i
+            fn.restype = C.c_long if name.endswith(("_ws_floats", "_scratch_bytes", "_sums_bytes", "_hist_bytes", "_zsplat_bytes", "_fill_bytes")) else _i
 
     # ---- helpers -----------------------------------------------------------------------------
     def version(self) -> str:
@@ -1830,6 +1839,98 @@ class PfLib:
         self._rc(self._dll.pf_trk_paint(_ptr(ids), _ptr(track), _ptr(track_map), _ptr(st_ids), B, H, W, M, self._stream(ids)),
                  "pf_trk_paint")
         return track_map
+
+    # ---- push-pull hole filling -----------------------------------------
+    def fill_levels(self, H: int, W: int) -> int:
+        self._have("pf_fill_levels")
+        r = self._dll.pf_fill_levels(H, W)
+        self._rc(min(r, 0), "pf_fill_levels")
+        return r
+
+    def fill_bytes(self, B: int, C_: int, H: int, W: int) -> int:
+        self._have("pf_fill_bytes")
+        r = self._dll.pf_fill_bytes(B, C_, H, W)
+        self._rc(min(r, 0), "pf_fill_bytes")
+        return r
+
+    def _chk_fill_in(self, what, src, hole, weight):
+        self._chk(src)
+        if src.dim() != 4:
+            raise PfError(f"{what}: src {tuple(src.shape)}, expected [B,C,H,W]")
+        B, Cc, H, W = src.shape
+        if hole is None:
+            raise PfError(f"{what}: hole is required")
+        self._chk_rp_bytes(what, (B, H, W), src.device, hole=hole)
+        self._chk_rp_maps(what, (B, H, W), src.device, weight=weight)
+        return B, Cc, H, W
+
+    def fill_pushpull(self, src, hole, weight, out, empty, scratch, stage: Optional[int] = None):
+        """pf_fill_pushpull: out fp32 [B,C,H,W] = src with the pixels of hole uint8 [B,H,W] (and those of weight fp32 [B,H,W] <= 0,
+        when given) filled from the pyramid; empty uint8 [B] or None; scratch: fill_bytes(B, C, H, W) bytes.  out may be src.
+        stage 0, 1 or 2: that stage alone (pf_fill_stage)."""
+        self._have("pf_fill_pushpull" if stage is None else "pf_fill_stage")
+        B, Cc, H, W = self._chk_fill_in("fill_pushpull", src, hole, weight)
+        dev = src.device
+        if out is None or scratch is None:
+            raise PfError("fill_pushpull: out and scratch are required")
+        self._chk_rp_maps("fill_pushpull", (B, Cc, H, W), dev, out=out)
+        self._chk_rp_bytes("fill_pushpull", (B,), dev, empty=empty)
+        self._chk_bytes(scratch, "fill_pushpull: scratch")
+        need = self.fill_bytes(B, Cc, H, W)
+        if scratch.device != dev or scratch.numel() * scratch.element_size() < need:
+            raise PfError(f"fill_pushpull: scratch holds {scratch.numel() * scratch.element_size()} bytes on {scratch.device}, "
+                          f"expected {need} on {dev}")
+        if stage is None:
+            self._rc(self._dll.pf_fill_pushpull(_ptr(src), _ptr(hole), _ptr(weight), _ptr(out), _ptr(empty), _ptr(scratch), B, Cc, H, W,
+                                                self._stream(src)), "pf_fill_pushpull")
+        else:
+            self._rc(self._dll.pf_fill_stage(_ptr(src), _ptr(hole), _ptr(weight), _ptr(out), _ptr(empty), _ptr(scratch), B, Cc, H, W,
+                                             int(stage), self._stream(src)), "pf_fill_stage")
+        return out
+
+    def fill_prepare(self, src, hole, weight, w0):
+        """pf_fill_prepare: the level-0 weight w0 fp32 [B,H,W] of src, hole and the optional weight."""
+        self._have("pf_fill_prepare")
+        B, Cc, H, W = self._chk_fill_in("fill_prepare", src, hole, weight)
+        if w0 is None:
+            raise PfError("fill_prepare: w0 is required")
+        self._chk_rp_maps("fill_prepare", (B, H, W), src.device, w0=w0)
+        self._rc(self._dll.pf_fill_prepare(_ptr(src), _ptr(hole), _ptr(weight), _ptr(w0), B, Cc, H, W, self._stream(src)),
+                 "pf_fill_prepare")
+        return w0
+
+    def fill_pull_level(self, fine_v, fine_w, coarse_v, coarse_w):
+        """pf_fill_pull_level: (coarse_v [B,C,Hc,Wc], coarse_w [B,Hc,Wc]) from (fine_v [B,C,Hf,Wf], fine_w [B,Hf,Wf])."""
+        self._have("pf_fill_pull_level")
+        self._chk(fine_v)
+        if fine_v.dim() != 4 or coarse_v is None or coarse_w is None or fine_w is None:
+            raise PfError("fill_pull_level: fine_v is [B,C,Hf,Wf]; every map is required")
+        B, Cc, Hf, Wf = fine_v.shape
+        Hc, Wc = max(1, (Hf + 1) // 2), max(1, (Wf + 1) // 2)
+        dev = fine_v.device
+        self._chk_rp_maps("fill_pull_level", (B, Hf, Wf), dev, fine_w=fine_w)
+        self._chk_rp_maps("fill_pull_level", (B, Cc, Hc, Wc), dev, coarse_v=coarse_v)
+        self._chk_rp_maps("fill_pull_level", (B, Hc, Wc), dev, coarse_w=coarse_w)
+        self._rc(self._dll.pf_fill_pull_level(_ptr(fine_v), _ptr(fine_w), _ptr(coarse_v), _ptr(coarse_w), B, Cc, Hf, Wf,
+                                              self._stream(fine_v)), "pf_fill_pull_level")
+
+    def fill_push_level(self, coarse_u, fine_v, fine_w, out, empty=None):
+        """pf_fill_push_level: out [B,C,Hf,Wf] (may be fine_v) from the filled level above coarse_u [B,C,Hc,Wc] (None at the 1 x 1
+        level: the apex step, which may write empty uint8 [B])."""
+        self._have("pf_fill_push_level")
+        self._chk(fine_v)
+        if fine_v.dim() != 4 or fine_w is None or out is None:
+            raise PfError("fill_push_level: fine_v is [B,C,Hf,Wf]; fine_w and out are required")
+        B, Cc, Hf, Wf = fine_v.shape
+        Hc, Wc = max(1, (Hf + 1) // 2), max(1, (Wf + 1) // 2)
+        dev = fine_v.device
+        self._chk_rp_maps("fill_push_level", (B, Hf, Wf), dev, fine_w=fine_w)
+        self._chk_rp_maps("fill_push_level", (B, Cc, Hf, Wf), dev, out=out)
+        self._chk_rp_maps("fill_push_level", (B, Cc, Hc, Wc), dev, coarse_u=coarse_u)
+        self._chk_rp_bytes("fill_push_level", (B,), dev, empty=empty)
+        self._rc(self._dll.pf_fill_push_level(_ptr(coarse_u), _ptr(fine_v), _ptr(fine_w), _ptr(out), _ptr(empty), B, Cc, Hf, Wf,
+                                              self._stream(fine_v)), "pf_fill_push_level")
+        return out
 
     # ---- self-supervised criterion (DESIGN.md section 21) --------------------------------------
     def selfsup_loss_batch(self, preds, image1, image2, weight, mask, i_weights, grads, partials, z: float, w_photo: float,

@@ -27,6 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import PfError
+from .inpaint import HoleFiller
 from .video import BidirectionalFlow
 
 
@@ -91,10 +92,12 @@ class FrameInterpolator:
     importance is exp(-min(alpha * m, zmax)) of its metric m.  alpha is a choice, not a measurement: at alpha * |residual| = 1
     a sample counts e^-1 against one whose round trip closes, so the default 1.0 discounts a sample by e per pixel of
     forward-backward residual.  A target pixel whose coverage (the blend weights that reached it, without the importance) is
-    below ``cmin`` is a hole: with fill "blend" it takes (1 - t) frame0 + t frame1 and stays flagged, with "none" it is 0.
+    below ``cmin`` is a hole: with fill "blend" it takes (1 - t) frame0 + t frame1 and stays flagged, with "none" it is 0, with
+    "pushpull" it is resolved as with "none" and then filled in place from the frame's own pyramid (``inpaint.HoleFiller``,
+    three more launches); ``hole`` stays as flagged.
     Values are clamped to +-vmax (declare the range of the frames: it fixes the scale of the integer sums)."""
 
-    FILLS = ("blend", "none")
+    FILLS = ("blend", "none", "pushpull")
 
     def __init__(self, B: int, C: int, H: int, W: int, device, alpha: float = 1.0, zmax: float = 12.0, cmin: float = 2.0 ** -10,
                  vmax: float = 255.0, fill: str = "blend", lib=None):
@@ -103,7 +106,7 @@ class FrameInterpolator:
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if fill not in self.FILLS:
-            raise PfError(f"FrameInterpolator: fill {fill!r}, expected 'blend' or 'none'")
+            raise PfError(f"FrameInterpolator: fill {fill!r}, expected one of {self.FILLS}")
         if min(B, H, W) < 1 or not 1 <= C <= 4:
             raise PfError(f"FrameInterpolator: B, C, H, W = {B}, {C}, {H}, {W} (C = 1..4)")
         if not (alpha >= 0 and zmax >= 0 and cmin > 0 and 1 <= vmax <= 65536):
@@ -114,6 +117,7 @@ class FrameInterpolator:
         self.acc = torch.zeros(B, C + 2, H, W, dtype=torch.int64, device=self.device)
         self.out = torch.zeros(B, C, H, W, dtype=torch.float32, device=self.device)
         self.hole = torch.zeros(B, H, W, dtype=torch.uint8, device=self.device)
+        self.filler = HoleFiller(B, C, H, W, self.device, lib=lib) if fill == "pushpull" else None
 
     def reset(self) -> None:
         """Zero the sums again (they are all-zero after every completed call; this is for a call that was cut short)."""
@@ -144,6 +148,8 @@ class FrameInterpolator:
             self.lib.splat_accumulate([(frame0, flow01, metric0, mask0, t, 1.0 - t), (frame1, flow10, metric1, mask1, 1.0 - t, t)],
                                       self.acc, self.alpha, self.zmax, self.vmax)
             self.lib.splat_resolve(self.acc, out, self.hole, 2, self.vmax, self.cmin, fills[0], fills[1], t)
+            if self.filler is not None:
+                self.filler.fill(out, self.hole, out=out)
         return out, self.hole
 
     def from_bidirectional(self, r: BidirectionalFlow, frame0, frame1, t: float, importance: Optional[str] = "residual",

@@ -30,6 +30,7 @@ import torch
 
 from ._lib import PfError
 from .egomotion import _device, _fit, _library, _on
+from .inpaint import HoleFiller
 from .odometry import Odometry
 
 DEFAULTS = dict(b_min=0.25, ztol_log2=0.25, w_max=8.0, cmin=0.5, n_min=1e-6, dmax=65536.0, vmax=255.0)
@@ -113,9 +114,11 @@ class Reprojector:
     """An inverse-depth map (and C = 0..4 payload planes) of B panoramas moved into the camera R X + T, with every buffer allocated
     here: ``run`` launches four times on the current stream (project, front, accumulate, resolve), allocates nothing, never
     synchronises and can be captured into a HIP graph.  It keeps ``flow``, ``d_new``, ``valid`` (the projection) and ``out``,
-    ``inv_depth``, ``weight``, ``hole`` (the result; overwritten by the next call)."""
+    ``inv_depth``, ``weight``, ``hole`` (the result; overwritten by the next call).  fill = True: six more launches close the holes
+    of the result from its own push-pull pyramid (``inpaint.HoleFiller``) into ``filled`` (of ``out``; None when C = 0) and
+    ``filled_inv_depth`` (of ``inv_depth``, with ``weight`` as the soft weight); the result itself stays as it is."""
 
-    def __init__(self, B: int, C: int, H: int, W: int, device, lib=None, **options):
+    def __init__(self, B: int, C: int, H: int, W: int, device, lib=None, fill: bool = False, **options):
         self.lib = _library(device, lib)
         self.device = _device(device)
         if min(B, H, W) < 1 or not 0 <= C <= 4:
@@ -132,11 +135,22 @@ class Reprojector:
         self.out = f32(B, C, H, W) if C else None
         self.inv_depth, self.weight = f32(B, H, W), f32(B, H, W)
         self.hole = torch.zeros(B, H, W, dtype=torch.uint8, device=dev)
+        if not isinstance(fill, bool):
+            raise PfError(f"Reprojector: fill = {fill!r}, expected True or False")
+        self.fill = fill
+        self.filled = self.filled_inv_depth = self.frame_filler = self.depth_filler = None
+        if fill:
+            self.depth_filler = HoleFiller(B, 1, H, W, dev, lib=lib)
+            self.filled_inv_depth = self.depth_filler.out.view(B, H, W)
+            if C:
+                self.frame_filler = HoleFiller(B, C, H, W, dev, lib=lib)
+                self.filled = self.frame_filler.out
 
     def reset(self) -> None:
         """Rewrite every buffer (the sums and the front are all-zero after every completed call; this is for one cut short)."""
         with _on(self.device):
-            for x in (self.acc, self.front, self.flow, self.d_new, self.valid, self.out, self.inv_depth, self.weight, self.hole):
+            for x in (self.acc, self.front, self.flow, self.d_new, self.valid, self.out, self.inv_depth, self.weight, self.hole,
+                      self.filled, self.filled_inv_depth):
                 if x is not None:
                     x.zero_()
 
@@ -148,6 +162,10 @@ class Reprojector:
                               o["w_max"], o["dmax"], o["vmax"])
         lib.zsplat_resolve(self.acc, self.front, self.out, self.inv_depth, self.weight, self.hole, o["cmin"], o["w_max"], o["dmax"],
                            o["vmax"])
+        if self.fill:
+            if self.frame_filler is not None:
+                self.frame_filler.fill(self.out, self.hole)
+            self.depth_filler.fill(self.inv_depth.view(self.B, 1, self.H, self.W), self.hole, self.weight)
 
     def run(self, src, inv_depth, weight, R, T, mask=None):
         """(out [B,C,H,W] or None, inv_depth, weight fp32 [B,H,W], hole uint8 [B,H,W]) in the later camera.  src: fp32 [B,C,H,W]
@@ -194,9 +212,11 @@ class DepthPropagator:
       ``predicted_inv_depth``, ``predicted_weight``, ``hole``, the state of the next push.
 
     channels = 3 and ``push(frame=previous)`` (fp32 [B,3,H,W]) also give ``predicted_frame``, the earlier frame rendered from the
-    later camera.  Options: ``Reprojector``'s, and tol_log2, decay of the filter."""
+    later camera.  fill = True also gives ``predicted_frame_filled`` and ``predicted_inv_depth_filled``, the two with their holes
+    closed (``Reprojector(fill=True)``); the state and the filter keep using the unfilled maps.  Options: ``Reprojector``'s, and
+    tol_log2, decay of the filter."""
 
-    def __init__(self, odo: Odometry, channels: int = 0, **options):
+    def __init__(self, odo: Odometry, channels: int = 0, fill: bool = False, **options):
         if not isinstance(odo, Odometry):
             raise PfError("DepthPropagator: odo is an Odometry")
         if channels not in (0, 1, 2, 3, 4):
@@ -204,7 +224,7 @@ class DepthPropagator:
         self.odo, self.lib, self.device = odo, odo.lib, odo.device
         self.B, self.H, self.W, self.C = odo.B, odo.H, odo.W, int(channels)
         self.f = _options("DepthPropagator", {k: v for k, v in options.items() if k in _FILTER_DEFAULTS}, _FILTER_DEFAULTS)
-        self.rp = Reprojector(self.B, self.C, self.H, self.W, self.device, lib=self.lib,
+        self.rp = Reprojector(self.B, self.C, self.H, self.W, self.device, lib=self.lib, fill=fill,
                               **{k: v for k, v in options.items() if k not in _FILTER_DEFAULTS})
         B, H, W, dev = self.B, self.H, self.W, self.device
         self.inv_depth = torch.zeros(B, H, W, dtype=torch.float32, device=dev)
@@ -214,6 +234,7 @@ class DepthPropagator:
         self.rigid_flow, self.valid = self.rp.flow, self.rp.valid
         self.predicted_inv_depth, self.predicted_weight, self.hole = self.rp.inv_depth, self.rp.weight, self.rp.hole
         self.predicted_frame = self.rp.out
+        self.predicted_frame_filled, self.predicted_inv_depth_filled = self.rp.filled, self.rp.filled_inv_depth
         self.reset()
 
     def reset(self) -> None:
