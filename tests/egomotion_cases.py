@@ -43,6 +43,38 @@ def rotation_flows(B, H, W, rot=0):
     return np.stack([er.flow_of(R, H, W) for R in Rs]).astype(np.float32), np.stack(Rs)
 
 
+MANY = 65          # the per-image kernels (solve, track) give a lane to an image: image 64 is the first of a second workgroup
+
+
+def many_rotation_flows(B, H, W, seed=17):
+    """(flow fp32 [B,2,H,W], R [B,3,3]): image b carries rotation b of small_rotations(B, seed), a different one per image."""
+    Rs = small_rotations(B, seed).astype(np.float64)
+    return np.stack([er.flow_of(R, H, W) for R in Rs]).astype(np.float32), Rs
+
+
+def grid_flows(B, H, W, seed):
+    """(flow fp32 [B,2,H,W], c, r int [B,H,W]): grid inputs.  Every end point is the centre of a pixel (r, c) with c >= x, reached by
+    u = c - x (or c - x - W where c > x, on a seeded half) and v = r - y, all whole numbers: x + u mod W and y + v are exact, so
+    both bearings of a pixel are built from cosf and sinf of the grid's own H + W angles and from nothing else."""
+    rng = np.random.default_rng(seed)
+    x, y = np.arange(W)[None, None, :], np.arange(H)[None, :, None]
+    c = rng.integers(np.broadcast_to(x, (B, H, W)), W)
+    r = rng.integers(0, H, (B, H, W))
+    u = (c - x) - np.where((rng.random((B, H, W)) < 0.5) & (c > x), W, 0)
+    return np.stack([u, r - y], 1).astype(np.float32), c, r
+
+
+def grid_agreement(lib, H, W, c, r, device):
+    """bool [B,H,W]: the pixels of grid_flows whose own row and column and whose end point's row and column are angles at which
+    `lib` on `device` and the host's math library give the same cosf and sinf, bit for bit.  The two sets of values are read off
+    pf_seg_tables, which evaluates pf_ego_row and pf_vp_theta's cosf and sinf and nothing else; a clamp of cos phi at 0 that changes
+    a value shows as a disagreement.  -> (agree, rows that agree [H], columns that agree [W])"""
+    import segments_cases as sc
+    (dr, dc), (hr, hc) = sc.tables(lib, H, W, device), sc.tables(sc.emu(), H, W)
+    ok_r, ok_c = (sc.bits(dr) == sc.bits(hr)).all(1), (sc.bits(dc) == sc.bits(hc)).all(1)
+    return ok_r[None, :, None] & ok_c[None, None, :] & ok_r[r] & ok_c[c], ok_r, ok_c
+
+
 def wound(flow, seed):
     """The same flow with u + W on a seeded quarter of the pixels and u - W on another."""
     rng = np.random.default_rng(seed)
@@ -129,17 +161,21 @@ def raw_sums(lib, flow, R, weighted, mask=None, device="cpu", scale_px=1.0, bloc
 
 
 def track(lib, Rs, smoothing, device="cpu"):
-    """The tracker over a sequence Rs [T,3,3] of one video: (orientations [T,3,3], corrections [T,3,3], states [T,8])."""
-    state = torch.zeros(1, 8, dtype=torch.float64, device=device)
+    """The tracker over a sequence Rs [T,3,3] of one video: (orientations [T,3,3], corrections [T,3,3], states [T,8]); over
+    Rs [T,B,3,3] of B videos in one batch: the same with [T,B,...]."""
+    Rs = np.asarray(Rs, np.float32)
+    one = Rs.ndim == 3
+    seq = _t(Rs[:, None] if one else Rs, device)
+    B = seq.shape[1]
+    state = torch.zeros(B, 8, dtype=torch.float64, device=device)
     state[:, 0::4] = 1.0
-    o = torch.zeros(1, 3, 3, device=device)
-    c = torch.zeros(1, 3, 3, device=device)
-    seq = _t(np.asarray(Rs, np.float32)[:, None], device)
+    o = torch.zeros(B, 3, 3, device=device)
+    c = torch.zeros(B, 3, 3, device=device)
     O, Cc, S = [], [], []
     for t in range(seq.shape[0]):
         lib.ego_track(seq[t], state, o, c, smoothing)
         O.append(o.clone()), Cc.append(c.clone()), S.append(state.clone())
-    return tuple(torch.cat(x).cpu().numpy() for x in (O, Cc, S))
+    return tuple((torch.cat(x) if one else torch.stack(x)).cpu().numpy() for x in (O, Cc, S))
 
 
 def rotate(lib, frame, R, device="cpu"):

@@ -49,6 +49,16 @@ def scene(B, H, W, depth="smooth", rot=0, tr=0, base=0):
     return flow, np.stack(Rs), np.stack(ts), np.stack([T / rho for T in Ts])
 
 
+def many_scenes(B, H, W):
+    """(flow, R_true, t_true) of B images, a different scene each: the 36 combinations of rotation, translation, baseline and depth
+    field, and from image 36 on the same again with a quarter of the columns wound one way and a quarter the other (seed b)."""
+    out = []
+    for b in range(B):
+        flow, R, t, _ = scene(1, H, W, ("smooth", "room")[(b // 18) % 2], rot=b, tr=b // 3, base=b // 9)
+        out.append((flow if b < 36 else ec.wound(flow, b), R, t))
+    return tuple(np.concatenate([o[i] for o in out]) for i in range(3))
+
+
 def robust_scene(H, W):
     """The issue's robust scene: smooth depth, rotation 0, translation 0, |T| = 0.3, and the block of pr.moved_block moved by a
     further (6, -2) px.  -> (flow fp32 [1,2,H,W], R_true, t_true, block [H,W] bool)"""

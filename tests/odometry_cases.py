@@ -80,6 +80,21 @@ def true_maps(bwd0, fwd1, mk, mk1, mapper):
     return mapper(bwd0[None], R0.T[None], (-R0.T @ t0)[None]), mapper(fwd1[None], R1[None], t1[None])
 
 
+def many_maps(B, H, W, mapper):
+    """Maps a and b [B,H,W] of B images under the true poses, a different scene per image: the nine pairs of motions, the four
+    ordered pairs of baselines whose ratio is no power of two (such a ratio puts l ON a bin edge) and the two depth fields, 72
+    combinations."""
+    pairs = ((0.1, 0.3), (0.3, 0.2), (0.2, 0.3), (0.3, 0.1))
+    assert B <= 72
+    maps = []
+    for b in range(B):
+        Ta, Tb = pairs[(b // 9) % 4]
+        mk, mk1 = motion(W, b, b // 3 + 1, Ta), motion(W, b + 1, b // 3, Tb)
+        _, bwd0, fwd1 = pair_flows(H, W, mk, mk1, ("smooth", "room")[(b // 36) % 2])
+        maps.append(true_maps(bwd0, fwd1, mk, mk1, mapper))
+    return tuple(tuple(np.concatenate([m[s][i] for m in maps]) for i in range(3)) for s in (0, 1))
+
+
 def ref_mapper(flow, R, t, mask=None):
     k, _, c, m, _ = pr.parallax(flow, np.asarray(R, np.float32), np.asarray(t, np.float32), mask)
     return k.astype(np.float32), c.astype(np.float32), m

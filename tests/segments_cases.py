@@ -23,6 +23,36 @@ POLE_FAMILIES = ("empty", "checker", "hstripes", "pole_scatter", "bernoulli_0.41
 # and a table beyond what the accumulate kernel keeps in LDS (512)
 SETTINGS = ((4, False, 8, 0.0), (8, False, 64, 1.5), (8, True, 64, 1.5), (4, True, 600, 0.0))
 
+# The paths that exist only on the device (tests/launch_paths.py), kept apart from SWEEP: (B, C, H, W), with B = TWO_PER_CU standing
+# for twice the card's CU count (512 on a whole MI355X, and for the host twin).
+#   (2 cus, 1, 24, 48)   the accumulate grid is capped at ONE workgroup per image: a full first trip and a second of 128 pixels
+#   (2, 3, 512, 1024)    the product size with both directions: 512 workgroups wanted against a cap of `cus`; the scan holds 2 rows
+#   (1, 1, 257, 66)      the scan holds 2 rows per thread, thread 128 holds one, the threads from 129 none; W = 64 + 2
+#   (1, 0, 600, 8)       3 rows per thread, the threads from 200 hold none; a map narrower than a wave
+TWO_PER_CU = "2cus"
+DEVICE_PATHS = ((TWO_PER_CU, 1, 24, 48), (2, 3, 512, 1024), (1, 1, 257, 66), (1, 0, 600, 8))
+# ... at the sweep's settings and at the two tables at their limits: the largest kept in LDS and PF_SEG_MAX_OBJECTS
+FULL_TABLES = ((8, False, 512, 0.0), (4, False, 4096, 0.0))
+DEVICE_SETTINGS = SETTINGS + FULL_TABLES
+DEVICE_FAMILIES = ("full", "serpentine", "hstripes", "junk", "bernoulli_0.41", "bernoulli_0.59")
+# where both new tables overflow (54 204 and 7 401 survivors per image against 4096 and 512 rows)
+OVERFLOWS = ((2, 3, 512, 1024), "bernoulli_0.41")
+ORDERS = (1, 2, 77, 123456789)                   # pf_emu_seg_order: reversed, and three shuffles
+
+
+def device_case(case, cus=256):
+    """(B, C, H, W) of one of DEVICE_PATHS on a card of `cus` CUs."""
+    return (2 * cus if case[0] == TWO_PER_CU else case[0],) + tuple(case[1:])
+
+
+def case_id(case):
+    return "x".join(str(n) for n in case)
+
+
+def device_combos(family):
+    """The settings a family of DEVICE_FAMILIES runs at: the pole settings apply to the horizontal stripes alone."""
+    return tuple(s for s in DEVICE_SETTINGS if not s[1] or family == "hstripes")
+
 
 def bits(a):
     a = np.ascontiguousarray(a)
@@ -191,8 +221,16 @@ def same_bits(a, b, what):
         assert not bad.any(), f"{what}: {k} differs in {int(bad.sum())} of {bad.size} cells, first at {np.argwhere(bad)[0].tolist()}"
 
 
-def reference(m, v, conn, poles, M, min_area, rows, cols, fault=None):
-    lab = sr.labels(m, conn, poles, fault)
+@functools.lru_cache(maxsize=None)
+def flood_fill(family, B, H, W, conn, poles):
+    """tests/segments_ref.py's labels of mask(family, B, H, W), once per connectivity: they do not depend on the table's size."""
+    lab = sr.labels(mask(family, B, H, W), conn, poles)
+    lab.setflags(write=False)
+    return lab
+
+
+def reference(m, v, conn, poles, M, min_area, rows, cols, fault=None, lab=None):
+    lab = sr.labels(m, conn, poles, fault) if lab is None else lab
     out = sr.objects(lab, rows, cols, v, M, min_area, fault)
     out["labels"] = lab
     return out

@@ -93,6 +93,79 @@ def test_same_bits_on_every_run_and_for_every_grid(lib):
             assert same(got, want), ((H, W), blocks)
 
 
+def _one_image_more_than_cus():
+    """(flow, mask, previous R) of CUs + 1 images on 6x10 maps, a different rotation per image, a tenth of the pixels junk."""
+    B, H, W = int(torch.cuda.get_device_properties(0).multi_processor_count) + 1, 6, 10
+    flow, bad = ec.poison(ec.many_rotation_flows(B, H, W, seed=23)[0], 3)
+    return flow, bad, ec.small_rotations(B, 29)
+
+
+def test_default_grid_with_no_workgroup_to_give(lib):
+    """One image more than the card has CUs: the default grid min(need, CUs / B) comes out at 0 and is raised to one workgroup per
+    image.  The raw sums of a plain and of a weighted pass are those of blocks = 1, bit for bit, and those of every 16th image
+    (and the last) are the sums of that image run alone, where the default grid has workgroups to spare."""
+    flow, bad, prev = _one_image_more_than_cus()
+    B = flow.shape[0]
+    for weighted in (False, True):
+        got = ec.raw_sums(lib, flow, prev, weighted, bad, "cuda")
+        assert got.any(1).all() and same([got], [ec.raw_sums(lib, flow, prev, weighted, bad, "cuda", blocks=1)]), weighted
+        for b in sorted(set(range(0, B, 16)) | {B - 1}):
+            one = ec.raw_sums(lib, flow[b:b + 1], prev[b:b + 1], weighted, bad[b:b + 1], "cuda")
+            assert np.array_equal(one[0], got[b]), (weighted, "image alone", b)
+
+
+def test_default_grid_sums_are_the_emulations(lib, emu):
+    """The same launch against the emulation, bit for bit, on grid inputs (ec.grid_flows): every end point is a pixel centre, so
+    both bearings come from cosf and sinf of the grid's own angles, and the pixels at whose angles the device's math library and the
+    host's part are masked for both sides (as tests/test_hip_odometry.py does with its rows of cos phi).  Every other step of
+    pf_ego_pixel is a correctly rounded fp32 operation on both sides.  On a scene with fractional end points the two libraries
+    part at some angle of every image and no sum can be asked to agree: there the sums are held to
+    blocks = 1 and to the image alone (the test above), here to all three."""
+    B, H, W = int(torch.cuda.get_device_properties(0).multi_processor_count) + 1, 6, 10
+    flow, c, r = ec.grid_flows(B, H, W, 31)
+    agree, ok_r, ok_c = ec.grid_agreement(lib, H, W, c, r, "cuda")
+    bad = (~agree | (np.random.default_rng(32).random((B, H, W)) < 0.1)).astype(np.uint8)
+    prev = ec.small_rotations(B, 29)
+    print(f"[egomotion] B = {B} (CUs + 1) grid inputs: cosf and sinf agree on {int(ok_r.sum())} of {H} rows and {int(ok_c.sum())} of {W} "
+          f"columns, {(bad == 0).mean():.1%} of the pixels used")
+    for weighted in (False, True):
+        got = ec.raw_sums(lib, flow, prev, weighted, bad, "cuda")
+        assert got[:, 11].all() and got[:, :9].any(1).all() and got[:, 10].all(), "an image without a used pixel or without a residual"
+        assert same([got], [ec.raw_sums(lib, flow, prev, weighted, bad, "cuda", blocks=1)]), weighted
+        want = ec.raw_sums(emu, flow, prev, weighted, bad)
+        differ = got != want
+        assert not differ.any(), (weighted, f"{int(differ.any(1).sum())} of {B} images, {int(differ.sum())} of {differ.size} cells differ",
+                                  np.nonzero(differ.any(1))[0][:8].tolist())
+
+
+def test_solve_and_track_beyond_a_wave_of_images(lib, emu):
+    """pf_ego_solve and pf_ego_track give a lane to an image, so image 64 is the first of a second workgroup: B = 65 on 6x10 maps,
+    a different rotation per image.  The estimate holds the float64 bounds and lies within them of the emulation's, the tracker
+    holds its bound over twelve frames, and image b of the batch is image b run alone, bit for bit."""
+    B, H, W = ec.MANY, 6, 10
+    flow, _ = ec.many_rotation_flows(B, H, W)
+    R, stats, sums = ec.estimate(lib, flow, device="cuda")
+    ref = er.Estimator(B, H, W).estimate(flow)
+    worst = ec.check_rotation(R, stats, ref, f"device B={B} {H}x{W}")
+    Re, se, _ = ec.estimate(emu, flow)
+    for b in range(B):
+        assert er.angle_between(R[b], Re[b]) <= er.rotation_bound(ref[1][b, 3]), b
+        Rb, sb, _ = ec.estimate(lib, flow[b:b + 1], device="cuda")
+        assert same([Rb[0], sb[0]], [R[b], stats[b]]), ("image alone", b)
+    assert same([stats[:, 2], stats[:, 4]], [se[:, 2], se[:, 4]]) and not sums.any() and stats[:, 4].all()
+    T = 12
+    Rs = np.stack([ec.small_rotations(T, 100 + b) for b in range(B)], 1)
+    O, Cc, S = ec.track(lib, Rs, 0.9, "cuda")
+    for b in range(B):
+        tref = er.Tracker(0.9)
+        for t in range(T):
+            ro, rc = tref.push(Rs[t, b])
+            assert np.abs(O[t, b] - ro).max() <= 2 * er.U and np.abs(Cc[t, b] - rc).max() <= 2 * er.U, (b, t)
+        Ob, Cb, Sb = ec.track(lib, Rs[:, b], 0.9, "cuda")
+        assert same([Ob, Cb], [O[:, b], Cc[:, b]]) and np.array_equal(Sb.view(np.uint64), S[:, b].view(np.uint64)), ("video alone", b)
+    print(f"[egomotion] device B={B} {H}x{W}: worst angle / bound {worst:.4f}")
+
+
 def test_poisoned_buffers_give_the_bits_of_a_fresh_estimator(lib):
     from prior_flow_amd.egomotion import RotationEstimator, Stabilizer
     B, H, W = 2, 33, 70

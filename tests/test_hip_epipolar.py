@@ -132,6 +132,75 @@ def test_same_bits_on_every_run_and_for_every_grid(lib):
             assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(got, want)), ((H, W), blocks)
 
 
+def _one_image_more_than_cus():
+    """(flow, mask, R, t, the three passes) of CUs + 1 images on 6x10 maps, a different scene per image, a tenth of the pixels junk."""
+    B, H, W = int(torch.cuda.get_device_properties(0).multi_processor_count) + 1, 6, 10
+    flow, R, t = pc.many_scenes(B, H, W)
+    flow, bad = pc.ec.poison(flow, 3)
+    return flow, bad, R, (("T", t, 0), ("R", t, 1), ("first T", None, 0))
+
+
+def test_default_grid_with_no_workgroup_to_give(lib):
+    """One image more than the card has CUs: the default grid min(need, CUs / B) comes out at 0 and is raised to one workgroup per
+    image.  The raw sums of a T pass, an R pass and a first T pass are those of blocks = 1, bit for bit, and those of every 16th
+    image (and the last) are the sums of that image run alone, where the default grid has workgroups to spare."""
+    flow, bad, R, passes = _one_image_more_than_cus()
+    B = flow.shape[0]
+    for name, tt, mode in passes:
+        got = pc.raw_sums(lib, flow, R, tt, mode, bad, "cuda")
+        assert got.any(1).all() and np.array_equal(got, pc.raw_sums(lib, flow, R, tt, mode, bad, "cuda", blocks=1)), name
+        for b in sorted(set(range(0, B, 16)) | {B - 1}):
+            one = pc.raw_sums(lib, flow[b:b + 1], R[b:b + 1], None if tt is None else tt[b:b + 1], mode, bad[b:b + 1], "cuda")
+            assert np.array_equal(one[0], got[b]), (name, "image alone", b)
+
+
+def test_default_grid_sums_are_the_emulations(lib, emu):
+    """The same launch against the emulation, bit for bit, on grid inputs (egomotion_cases.grid_flows): every end point is a pixel
+    centre, so both bearings come from cosf and sinf of the grid's own angles, and the pixels at whose angles the device's math
+    library and the host's part are masked for both sides (as tests/test_hip_odometry.py does with its rows of cos phi).  Every
+    other step of pf_epi_pixel is a correctly rounded fp32 operation (+, -, *, /, sqrtf) on both sides.  On a scene with fractional
+    end points the two libraries part at some angle of every image and no sum can be asked to agree (the head of this file):
+    there the sums are held to blocks = 1 and to the image alone (the test above), here to all three."""
+    B, H, W = int(torch.cuda.get_device_properties(0).multi_processor_count) + 1, 6, 10
+    flow, c, r = pc.ec.grid_flows(B, H, W, 41)
+    agree, ok_r, ok_c = pc.ec.grid_agreement(lib, H, W, c, r, "cuda")
+    bad = (~agree | (np.random.default_rng(42).random((B, H, W)) < 0.1)).astype(np.uint8)
+    _, R, t = pc.many_scenes(B, H, W)
+    print(f"[epipolar] B = {B} (CUs + 1) grid inputs: cosf and sinf agree on {int(ok_r.sum())} of {H} rows and {int(ok_c.sum())} of {W} "
+          f"columns, {(bad == 0).mean():.1%} of the pixels used")
+    for name, tt, mode in (("T", t, 0), ("R", t, 1), ("first T", None, 0)):
+        got = pc.raw_sums(lib, flow, R, tt, mode, bad, "cuda")
+        assert got[:, 12].all() and got[:, ([0, 3, 5] if mode == 0 else [13, 16, 18])].any(1).all(), (name, "an image without a used pixel")
+        assert np.array_equal(got, pc.raw_sums(lib, flow, R, tt, mode, bad, "cuda", blocks=1)), name
+        want = pc.raw_sums(emu, flow, R, tt, mode, bad)
+        differ = got != want
+        assert not differ.any(), (name, f"{int(differ.any(1).sum())} of {B} images, {int(differ.sum())} of {differ.size} cells differ",
+                                  np.nonzero(differ.any(1))[0][:8].tolist())
+
+
+def test_solve_beyond_a_wave_of_images(lib, emu):
+    """pf_epi_solve (and pf_ego_solve before it) give a lane to an image, so image 64 is the first of a second workgroup: B = 65 on
+    6x10 maps, a different scene per image.  Every launch holds the float64 bounds, the answer lies within the single-launch bound
+    of the emulation's, and image b of the batch is image b run alone, bit for bit."""
+    B, H, W = pc.ec.MANY, 6, 10
+    flow, _, _ = pc.many_scenes(B, H, W)
+    steps = pc.stepwise(lib, flow, device="cuda")
+    worst = pc.check_steps(steps, flow, what=f"device B={B} {H}x{W}")
+    got = pc.estimate(lib, flow, device="cuda")
+    assert all(np.array_equal(bits(got[k]), bits(steps[-1][i])) for k, i in (("R", 2), ("t", 3), ("stats", 4)))
+    assert not got["sums"].any() and not got["ego_sums"].any()
+    e = pc.estimate(emu, flow)
+    ref = pr.Pose(B, H, W)
+    _, rt, rst = ref.step("T", False, flow, None, steps[-2][2].astype(np.float64), steps[-2][3].astype(np.float64), None)
+    assert np.array_equal(e["stats"][:, 5], got["stats"][:, 5]) and np.array_equal(bits(e["stats"][:, 2]), bits(got["stats"][:, 2]))
+    for b in range(B):
+        if rst[b, 5]:
+            assert pr.angle_vec(e["t"][b], got["t"][b]) <= 2 * pr.t_pass_bound(rst[b], ref.last_t[b], W), b
+        one = pc.estimate(lib, flow[b:b + 1], device="cuda")
+        assert all(np.array_equal(bits(one[k][0]), bits(got[k][b])) for k in ("R", "t", "stats", "R0")), ("image alone", b)
+    print(f"[epipolar] device B={B} {H}x{W}: worst error / bound {worst:.2e}, {int(got['stats'][:, 5].sum())} of {B} fits valid")
+
+
 def test_poisoned_buffers_give_the_bits_of_a_fresh_estimator(lib):
     B, H, W = 2, 33, 70
     flow, _, _, _ = pc.scene(B, H, W)

@@ -240,6 +240,66 @@ def test_same_bits_on_every_run_and_for_every_grid(lib, emu, bins):
             against_emulation(want, e, ma, mb, bins, f"{name} {H}x{W} bins {bins}")
 
 
+@pytest.mark.parametrize("bins", (64, 512))
+def test_default_grid_with_no_workgroup_to_give(lib, emu, bins):
+    """One image more than the card has CUs: the default grid min(need, CUs / B) comes out at 0 and is raised to one workgroup per
+    image.  On grid inputs with whole l, the rows where the two cosf part marked moving (as in test_device_grid_inputs_bit_for_bit),
+    the cells, ratio and stats are those of blocks = 1 and the emulation's, bit for bit."""
+    import ctypes
+    B, H, W = int(torch.cuda.get_device_properties(0).multi_processor_count) + 1, 6, 10
+    host = (ctypes.c_float * H)()
+    emu._dll.pf_emu_odo_rows(H, host)
+    agree = bits(np.array(host[:], np.float32)) == bits(oc.rows_of(lib, H, W, DEV))
+    ma, mb, _ = oc.grid_maps(B, H, W, bins, 4.0, 13, integer=True)
+    ma = (ma[0], ma[1], ma[2] | (~agree)[None, :, None].astype(np.uint8))
+    got = oc.link_run(lib, ma, mb, DEV, bins=bins)
+    print(f"[odometry] B = {B} (CUs + 1) bins {bins}: cos phi agrees on {int(agree.sum())} of {H} rows")
+    assert agree.any() and got[2][:, 2 * bins + 1].all() and same(got, oc.link_run(lib, ma, mb, DEV, blocks=1, bins=bins))
+    assert same(got, oc.link_run(emu, ma, mb, bins=bins))
+
+
+def test_solve_reverse_and_track_beyond_a_wave_of_images(lib, emu):
+    """pf_odo_solve, pf_odo_reverse_pose and pf_odo_track give a lane to an image, so image 64 is the first of a second workgroup:
+    B = 65, a different scene per image on 6x10 maps.  The comparisons of test_device_link_matches_float64_and_the_emulation and of
+    test_device_track_reverse_and_fuse_match_float64, and image b of the batch is image b run alone, bit for bit."""
+    B, H, W = 65, 6, 10
+    ma, mb = oc.many_maps(B, H, W, oc.lib_mapper(lib, DEV))
+    for bins in (64, 512):
+        got = oc.link_run(lib, ma, mb, DEV, bins=bins)
+        oc.check_link(got, ma, mb, f"device B={B} {H}x{W} bins {bins}", bins=bins)
+        for b in range(B):
+            one = oc.link_run(lib, tuple(x[b:b + 1] for x in ma), tuple(x[b:b + 1] for x in mb), DEV, bins=bins)
+            assert np.array_equal(one[2][0], got[2][b]) and np.array_equal(bits(one[0]), bits(got[0][b:b + 1])) \
+                and np.array_equal(bits(one[1][0]), bits(got[1][b])), ("image alone", bins, b)
+        against_emulation(got, oc.link_run(emu, ma, mb, bins=bins), ma, mb, bins, f"B={B} {H}x{W} bins {bins}")
+    n = 6
+    rng = np.random.default_rng(14)
+    run, ref, alone = oc.TrackRun(lib, B, DEV), orf.Track(B), [oc.TrackRun(lib, 1, DEV) for _ in range(B)]
+    for k in range(n):
+        R = np.stack([er.axis_angle(rng.normal(size=3), rng.uniform(0, 40)) for _ in range(B)]).astype(np.float32)
+        t = np.stack([pr.unit(rng.normal(size=3)) for _ in range(B)]).astype(np.float32)
+        pv, lv = rng.random(B) < 0.8, rng.random(B) < 0.8
+        ratio = np.exp2(rng.uniform(-1, 1, B)).astype(np.float32)
+        t[~pv] = 0
+        got = run.step(R, t, pv, ratio, lv)
+        go, gc_, gs, gf = got
+        ro, rc, rs, rf = ref.step(R, t, pv, ratio, lv)
+        size = max(1.0, float(np.abs(rc).max()))
+        assert np.array_equal(gf, rf), (k, gf, rf)
+        assert np.abs(go - ro).max() <= 8 * er.U * (k + 1) and np.abs(gc_ - rc).max() <= 8 * er.U * (k + 1) * size, k
+        assert (np.abs(gs / rs - 1) <= 8 * er.U * (k + 1)).all()
+        Rr, tr = oc.reverse_run(lib, R, t, DEV)
+        assert np.array_equal(bits(Rr), bits(np.ascontiguousarray(R.transpose(0, 2, 1)))) and np.abs(tr - orf.reverse_pose(R, t)[1]).max() <= 8 * er.U
+        assert not np.signbit(tr[~pv]).any() and not tr[~pv].any()
+        for b in range(B):
+            one = alone[b].step(R[b:b + 1], t[b:b + 1], pv[b:b + 1], ratio[b:b + 1], lv[b:b + 1])
+            assert all(np.array_equal(bits(o[0]), bits(g[b])) for o, g in zip(one, got)), ("video alone", k, b)
+            R1, t1 = oc.reverse_run(lib, R[b:b + 1], t[b:b + 1], DEV)
+            assert np.array_equal(bits(R1[0]), bits(Rr[b])) and np.array_equal(bits(t1[0]), bits(tr[b])), ("pose alone", k, b)
+    state = run.state.cpu().numpy()
+    assert all(np.array_equal(bits(alone[b].state.cpu().numpy()[0]), bits(state[b])) for b in range(B)), "the kept state"
+
+
 def test_poisoned_state_and_reset_on_the_device(lib):
     from prior_flow_amd.odometry import Odometry
     H, W = 32, 64

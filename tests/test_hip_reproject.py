@@ -80,6 +80,26 @@ def test_device_update(lib, emu, B, H, W):
     assert all((bits(a) == bits(b)).all() for a, b in zip(got, unaligned)), "the element form gives the quad form's bits"
 
 
+def test_device_update_beyond_a_wave_of_images(lib, emu):
+    """pf_depth_update's segment pass gives a lane to an image, so image 64 is the first of a second workgroup: B = 65 on 6x10
+    maps, every second image (the last one too) changing its segment.  The comparisons of test_device_update, and image b of the
+    batch is image b run alone, bit for bit."""
+    B, H, W = 65, 6, 10
+    ds, ws, dm, wm, dis = rc.update_inputs(B, H, W, 65)
+    flags = np.array([[3, 2 + b % 3, 1, 1] for b in range(B)], np.int32)    # the segment each image is in now
+    seg = np.where(np.arange(B) % 2 == 0, 1, flags[:, 1]).astype(np.int32)
+    got = rc.update_run(lib, ds, ws, dm, wm, dis, flags, seg, DEV)
+    differ, worst, edge = th.check_update(got, ds, ws, dm, wm, dis, flags, seg, f"device update {B}x{H}x{W}")
+    want = rc.update_run(emu, ds, ws, dm, wm, dis, flags, seg)
+    apart = int((bits(got[0]) != bits(want[0])).sum() + (bits(got[1]) != bits(want[1])).sum())
+    print(f"[reproject] device update {B}x{H}x{W}: worst error / bound {worst:.3f}; {differ} values differ from the fp32 restatement, "
+          f"{apart} from the emulation, {edge} at the edge of tol")
+    assert differ == 0 and apart == 0 and (got[2] == want[2]).all() and (got[2] == flags[:, 1]).all()
+    for b in range(B):
+        one = rc.update_run(lib, *(x[b:b + 1] for x in (ds, ws, dm, wm, dis, flags, seg)), DEV)
+        assert all((bits(o[0]) == bits(g[b])).all() for o, g in zip(one, got)), ("image alone", b)
+
+
 def test_device_update_rules(lib):
     th.update_rules(lib, DEV)
 

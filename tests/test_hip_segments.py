@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import golden_cases as gc
+import launch_paths as lp
 import segments_cases as sc
 import segments_ref as sr
 
@@ -41,6 +42,23 @@ def _table_within_bound(got, what):
     return worst
 
 
+def _device_against_emulation(lib, emu, m, v, setting, tabs, what):
+    """One update on the device and in the emulation: every integer bit for bit, the table within the bound, and a second run,
+    maps offset by one element and poisoned buffers give the same bits.  -> (worst table error / bound, the device's arrays)."""
+    conn, poles, M, min_area = setting
+    W = m.shape[2]
+    got = sc.run(lib, m, v, conn, poles, M, min_area, DEV, tabs=tabs)
+    want = sc.run(emu, m, v, conn, poles, M, min_area, tabs=tabs)
+    for k in ("labels", "ids", "keep", "roots", "count", "sums"):
+        bad = sc.bits(got[k]) != sc.bits(want[k])
+        assert not bad.any(), f"{what}: {k} differs in {int(bad.sum())} of {bad.size} cells, first at {np.argwhere(bad)[0].tolist()}"
+    worst = max(_table_within_bound(got, what), sr.table_error(got["table"], want["table"].astype(np.float64), _bound_of(got), W))
+    sc.same_bits(sc.run(lib, m, v, conn, poles, M, min_area, DEV, tabs=tabs), got, f"second run: {what}")
+    sc.same_bits(sc.run(lib, m, v, conn, poles, M, min_area, DEV, offset=1, tabs=tabs), got, f"unaligned maps: {what}")
+    sc.same_bits(sc.run(lib, m, v, conn, poles, M, min_area, DEV, tabs=tabs, poison=True), got, f"poisoned buffers: {what}")
+    return worst, got
+
+
 @pytest.mark.parametrize("B,C,H,W", sc.SWEEP)
 def test_device_matches_the_emulation(lib, emu, B, C, H, W):
     tabs = sc.tables(lib, H, W, DEV)
@@ -48,20 +66,54 @@ def test_device_matches_the_emulation(lib, emu, B, C, H, W):
     worst, runs = 0.0, 0
     for family in sc.FAMILIES:
         m = sc.mask(family, B, H, W)
-        for conn, poles, M, min_area in sc.combos(family):
-            what = f"device {family} {B}x{C}x{H}x{W} {(conn, poles, M, min_area)}"
-            got = sc.run(lib, m, v, conn, poles, M, min_area, DEV, tabs=tabs)
-            want = sc.run(emu, m, v, conn, poles, M, min_area, tabs=tabs)
-            for k in ("labels", "ids", "keep", "roots", "count", "sums"):
-                bad = sc.bits(got[k]) != sc.bits(want[k])
-                assert not bad.any(), f"{what}: {k} differs in {int(bad.sum())} of {bad.size} cells, first at {np.argwhere(bad)[0].tolist()}"
-            worst = max(worst, _table_within_bound(got, what), sr.table_error(got["table"], want["table"].astype(np.float64),
-                                                                              _bound_of(got), W))
-            sc.same_bits(sc.run(lib, m, v, conn, poles, M, min_area, DEV, tabs=tabs), got, f"second run: {what}")
-            sc.same_bits(sc.run(lib, m, v, conn, poles, M, min_area, DEV, offset=1, tabs=tabs), got, f"unaligned maps: {what}")
-            sc.same_bits(sc.run(lib, m, v, conn, poles, M, min_area, DEV, tabs=tabs, poison=True), got, f"poisoned buffers: {what}")
+        for setting in sc.combos(family):
+            what = f"device {family} {B}x{C}x{H}x{W} {setting}"
+            worst = max(worst, _device_against_emulation(lib, emu, m, v, setting, tabs, what)[0])
             runs += 1
     print(f"[segments] device {B}x{C}x{H}x{W}: {runs} cases, worst table error / bound {worst:.3f}")
+
+
+def _cus():
+    return int(torch.cuda.get_device_properties(0).multi_processor_count)
+
+
+# what each of sc.DEVICE_PATHS is there for (tests/launch_paths.py); the second trip of the product size hangs on the card's CUs
+REACHES = {
+    (sc.TWO_PER_CU, 1, 24, 48): {"accumulate_second_trip_lds", "accumulate_second_trip_global"},
+    (2, 3, 512, 1024): {"scan_two_rows_per_thread"},
+    (1, 1, 257, 66): {"scan_two_rows_per_thread", "scan_clipped_threads"},
+    (1, 0, 600, 8): {"scan_two_rows_per_thread", "scan_clipped_threads"},
+}
+
+
+@pytest.mark.parametrize("family", sc.DEVICE_FAMILIES)
+@pytest.mark.parametrize("case", sc.DEVICE_PATHS, ids=sc.case_id)
+def test_device_matches_the_emulation_on_the_device_only_paths(lib, emu, case, family):
+    """The launch rules that no emulation restates: an accumulate grid capped by the CU count, whose workgroups go round their loop
+    again and flush their LDS partials (or their global atomics) once after it; a scan in which a thread holds two or three rows
+    and the last threads are clipped; the tables at 512 (the largest kept in LDS) and at PF_SEG_MAX_OBJECTS, both full."""
+    cus = _cus()
+    B, C, H, W = sc.device_case(case, cus)
+    reached = set().union(*(lp.seg_device_paths(B, C, H, W, s[2], cus) for s in sc.device_combos(family)))
+    print(f"[segments] device paths {lp.describe_seg(B, C, H, W, cus)}; reached: {sorted(reached)}")
+    assert REACHES[case] <= reached, f"{B}x{C}x{H}x{W} on {cus} CUs reaches {sorted(reached)}"
+    if case == sc.OVERFLOWS[0]:
+        assert cus >= 512 or {"accumulate_second_trip_lds", "accumulate_second_trip_global"} <= reached
+    assert {"table_512", "table_4096"} <= reached
+    if case == (1, 1, 257, 66):
+        assert lp.seg_scan_rows_per_thread(H) == 2 and lp.seg_scan_rows_of_thread(H, 128) == 1 and lp.clipped_threads(H)[1] == 129
+    if case == (1, 0, 600, 8):
+        assert lp.seg_scan_rows_per_thread(H) == 3 and lp.clipped_threads(H)[0] == 200 and lp.seg_scan_rows_of_thread(H, 200) == 0
+    tabs = sc.tables(lib, H, W, DEV)
+    m, v = sc.mask(family, B, H, W), sc.values(B, C, H, W)
+    worst = 0.0
+    for setting in sc.device_combos(family):
+        what = f"device {family} {B}x{C}x{H}x{W} {setting}"
+        w, got = _device_against_emulation(lib, emu, m, v, setting, tabs, what)
+        worst = max(worst, w)
+        if (case, family) == sc.OVERFLOWS and setting in sc.FULL_TABLES:
+            assert (got["count"] > setting[2]).all() and (got["roots"] >= 0).all(), f"{what}: the table is not full"
+    print(f"[segments] device {B}x{C}x{H}x{W} {family}: {len(sc.device_combos(family))} settings, worst table error / bound {worst:.3f}")
 
 
 def _bound_of(got):

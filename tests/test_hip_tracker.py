@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import golden_cases as gc
+import launch_paths as lp
 import segments_cases as sc
 import tracker_cases as tc
 
@@ -39,19 +40,60 @@ def test_device_matches_the_emulation(lib, emu, B, H, W):
             o0, o1 = (tc.objects(lab, rows, cols, M, min_area) for lab in p["labels"])
             for direction in tc.DIRECTIONS:
                 what = f"device {family} {B}x{H}x{W} M={M} {direction}"
-                got = tc.run_pair(lib, p, o0, o1, rows, direction, M, DEV, ref=False)
-                want = tc.run_pair(emu, p, o0, o1, rows, direction, M, ref=False)
-                for k, (g, w) in enumerate(zip(got, want)):
-                    ints = tc.INT_KEYS + tc.STATE_KEYS[:-1]
-                    tc.same_bits({n: g[n] for n in ints}, {n: w[n] for n in ints}, f"{what} push {k + 1}")
-                    worst = max(worst, tc.within_bound(g, w, f"{what} push {k + 1}"))
-                    assert sc.bits(g["st_path"]).tolist() == sc.bits(g["path"]).tolist()
-                for name, kw in (("second run", {}), ("maps offset by one element", dict(offset=1)), ("poisoned outputs", dict(poison=True))):
-                    again = tc.run_pair(lib, p, o0, o1, rows, direction, M, DEV, ref=False, **kw)
-                    for k in (0, 1):
-                        tc.same_bits(again[k], got[k], f"{name}: {what} push {k + 1}")
+                worst = max(worst, _device_against_emulation(lib, emu, p, o0, o1, rows, direction, M, what))
                 runs += 1
     print(f"[tracker] device {B}x{H}x{W}: {runs} pairs, worst step / path difference / (2 x bound) {worst:.3f}")
+
+
+def _device_against_emulation(lib, emu, p, o0, o1, rows, direction, M, what):
+    """Two pushes on the device and in the emulation: every integer and the kept state bit for bit, step and path within twice the
+    bound; a second run, maps offset by one element and poisoned outputs give the same bits.  -> worst difference / (2 x bound)."""
+    worst = 0.0
+    got = tc.run_pair(lib, p, o0, o1, rows, direction, M, DEV, ref=False)
+    want = tc.run_pair(emu, p, o0, o1, rows, direction, M, ref=False)
+    for k, (g, w) in enumerate(zip(got, want)):
+        ints = tc.INT_KEYS + tc.STATE_KEYS[:-1]
+        tc.same_bits({n: g[n] for n in ints}, {n: w[n] for n in ints}, f"{what} push {k + 1}")
+        worst = max(worst, tc.within_bound(g, w, f"{what} push {k + 1}"))
+        assert sc.bits(g["st_path"]).tolist() == sc.bits(g["path"]).tolist()
+    for name, kw in (("second run", {}), ("maps offset by one element", dict(offset=1)), ("poisoned outputs", dict(poison=True))):
+        again = tc.run_pair(lib, p, o0, o1, rows, direction, M, DEV, ref=False, **kw)
+        for k in (0, 1):
+            tc.same_bits(again[k], got[k], f"{name}: {what} push {k + 1}")
+    return worst
+
+
+def _cus():
+    return int(torch.cuda.get_device_properties(0).multi_processor_count)
+
+
+@pytest.mark.parametrize("direction", tc.DIRECTIONS)
+@pytest.mark.parametrize("family", tc.DEVICE_FAMILIES)
+@pytest.mark.parametrize("case", tc.DEVICE_PATHS, ids=sc.case_id)
+def test_device_matches_the_emulation_on_the_device_only_paths(lib, emu, case, family, direction):
+    """The launch rules that no emulation restates: a vote grid capped by the CU count, whose workgroups go round their loop again
+    (at twice the card's CUs in images a single workgroup of 16 waves takes 24 items, so half its waves find nothing the second
+    time) and flush their LDS matrix or their global atomics after it; the table at PF_TRK_MAX_OBJECTS, where every thread of the
+    match kernel owns a slot and the scan's last element is a real object."""
+    cus = _cus()
+    B, H, W = tc.device_case(case, cus)
+    reached = set().union(*(lp.trk_device_paths(B, H, W, s[0], cus) for s in tc.DEVICE_SETTINGS))
+    print(f"[tracker] device paths {lp.describe_trk(B, H, W, cus)}; reached: {sorted(reached)}")
+    assert "table_256" in reached
+    if case[0] == sc.TWO_PER_CU:
+        assert lp.trk_vote_grid(B, H, W, cus) == (2, 1) and H * ((W + 63) // 64) == 24
+    if case[0] == sc.TWO_PER_CU or cus < 512:
+        assert {"vote_second_trip_lds", "vote_second_trip_global"} <= reached, f"{B}x{H}x{W} on {cus} CUs reaches {sorted(reached)}"
+    small, full = tc.device_pair(family, B, H, W)
+    rows, cols = sc.tables(lib, H, W, DEV)
+    worst = 0.0
+    for M, min_area in tc.DEVICE_SETTINGS:
+        o0, o1 = (tc.objects(lab, rows, cols, M, min_area) for lab in small["labels"])
+        if (case, family) == tc.OVERFLOWS and (M, min_area) == tc.FULL_TABLE:
+            assert (o0[1] > M).all() and (o1[1] > M).all(), "the table of 256 is not full in both frames"
+        what = f"device {family} {B}x{H}x{W} M={M} {direction}"
+        worst = max(worst, _device_against_emulation(lib, emu, full, tc.tiled(o0, B), tc.tiled(o1, B), rows, direction, M, what))
+    print(f"[tracker] device {B}x{H}x{W} {family} {direction}: worst step / path difference / (2 x bound) {worst:.3f}")
 
 
 def _bits(tk):

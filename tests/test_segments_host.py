@@ -37,6 +37,36 @@ def test_emulation_matches_the_flood_fill(emu, B, C, H, W):
     print(f"[segments] emulation {B}x{C}x{H}x{W}: {runs} runs, worst table error / bound {worst:.3f}")
 
 
+@pytest.mark.parametrize("family", sc.DEVICE_FAMILIES)
+@pytest.mark.parametrize("case", sc.DEVICE_PATHS, ids=sc.case_id)
+def test_emulation_matches_the_flood_fill_at_the_device_path_cases(emu, case, family):
+    """The host twin of tests/test_hip_segments.py's cases for the device-only paths (a capped grid, a scan of several rows per
+    thread, the tables at their limits), at B = 512 for twice a whole card's CUs: the restatement is held to the flood fill before
+    a device is held to the restatement.  Under sc.OVERFLOWS both new tables must be full, whatever becomes of the masks."""
+    B, C, H, W = sc.device_case(case)
+    m, v = sc.mask(family, B, H, W), sc.values(B, C, H, W)
+    worst = 0.0
+    for setting in sc.device_combos(family):
+        conn, poles, M, min_area = setting
+        what = f"{family} {B}x{C}x{H}x{W} {setting}"
+        got = sc.run(emu, m, v, conn, poles, M, min_area)
+        ref = sc.reference(m, v, conn, poles, M, min_area, got["rows"], got["cols"], lab=sc.flood_fill(family, B, H, W, conn, poles))
+        worst = max(worst, sc.against_reference(got, ref, what))
+        if (case, family) == sc.OVERFLOWS and setting in sc.FULL_TABLES:
+            print(f"[segments] {what}: survivors per image {got['count'].tolist()}")
+            assert (got["count"] > M).all() and (got["roots"] >= 0).all(), f"{what}: the table is not full"
+        if setting in sc.FULL_TABLES or poles:
+            try:
+                for seed in sc.ORDERS:
+                    emu._dll.pf_emu_seg_order(seed)
+                    sc.same_bits(sc.run(emu, m, v, conn, poles, M, min_area), got, f"{what} order {seed}")
+            finally:
+                emu._dll.pf_emu_seg_order(0)
+    if family == "full":
+        assert (got["labels"] == 1).all()
+    print(f"[segments] emulation {B}x{C}x{H}x{W} {family}: worst table error / bound {worst:.3f}")
+
+
 def test_checkerboard_counts(emu):
     """One component at 8; every pixel its own at 4; at odd W the seam joins two columns of equal parity."""
     for H, W in ((6, 10), (6, 11)):

@@ -46,6 +46,29 @@ def test_emulation_matches_the_reference(emu, B, H, W):
     print(f"[tracker] emulation {B}x{H}x{W}: {runs} pairs, worst step / path error / bound {worst:.3f}")
 
 
+@pytest.mark.parametrize("family", tc.DEVICE_FAMILIES)
+@pytest.mark.parametrize("case", tc.DEVICE_PATHS, ids=sc.case_id)
+def test_emulation_matches_the_reference_at_the_device_path_cases(emu, case, family):
+    """The host twin of tests/test_hip_tracker.py's cases for the device-only paths (a capped vote grid, the table at
+    PF_TRK_MAX_OBJECTS), at B = 512 for twice a whole card's CUs.  At the product size the full table really is full."""
+    B, H, W = tc.device_case(case)
+    small, full = tc.device_pair(family, B, H, W)
+    rows, cols = sc.tables(emu, H, W)
+    worst, runs = 0.0, 0
+    for M, min_area in tc.DEVICE_SETTINGS:
+        o0, o1 = (tc.objects(lab, rows, cols, M, min_area) for lab in small["labels"])
+        if (case, family) == tc.OVERFLOWS and (M, min_area) == tc.FULL_TABLE:
+            print(f"[tracker] {family} {B}x{H}x{W} M={M}: objects per image {o0[1].tolist()} and {o1[1].tolist()}")
+            assert (o0[1] > M).all() and (o1[1] > M).all(), "the table of 256 is not full in both frames"
+        for direction in tc.DIRECTIONS:
+            what = f"{family} {B}x{H}x{W} M={M} {direction}"
+            g1, g2, (r1, n1), (r2, n2) = tc.run_pair_tiled(emu, small, full, o0, o1, rows, direction, M)
+            worst = max(worst, tc.against_reference(g1, r1, n1, what + " push 1"), tc.against_reference(g2, r2, n2, what + " push 2"))
+            runs += 1
+            assert g2["votes"].any(), what
+    print(f"[tracker] emulation {B}x{H}x{W} {family}: {runs} pairs, worst step / path error / bound {worst:.3f}")
+
+
 @pytest.mark.parametrize("family,B,H,W,M", (("bernoulli_0.5", 2, 64, 128, 64), ("junk", 1, 33, 70, 8), ("bernoulli_0.41", 1, 40, 1100, 200)))
 def test_votes_do_not_depend_on_the_order_of_the_pixels(emu, family, B, H, W, M):
     p = tc.pair(family, B, H, W)

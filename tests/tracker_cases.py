@@ -26,6 +26,16 @@ DIRECTIONS = ("forward", "backward", "both")
 FAMILIES = ("static", "shift", "seam", "swap", "split", "tie", "merge", "birth_death", "masked", "junk", "bernoulli_0.41",
             "bernoulli_0.5")
 MIN_OVERLAP = 0.25
+# The paths that exist only on the device (tests/launch_paths.py), kept apart from SHAPES: (B, H, W), B = sc.TWO_PER_CU standing for
+# twice the card's CU count.
+#   (2 cus, 24, 48)    24 items against a cap of ONE workgroup of 16 waves: a second trip in which half the waves have nothing
+#   (2, 512, 1024)     the product size: 512 workgroups wanted against a cap of `cus`
+DEVICE_PATHS = ((sc.TWO_PER_CU, 24, 48), (2, 512, 1024))
+FULL_TABLE = (256, 0.0)                          # PF_TRK_MAX_OBJECTS: every thread of the match kernel owns a slot
+DEVICE_SETTINGS = SETTINGS + (FULL_TABLE,)
+DEVICE_FAMILIES = ("shift", "seam", "split", "junk", "bernoulli_0.41")
+OVERFLOWS = ((2, 512, 1024), "bernoulli_0.41")   # more than 256 objects in both frames
+DISTINCT = 8                                     # a large batch repeats its first DISTINCT images: image b is image b % DISTINCT
 INT_KEYS = ("votes", "track", "age", "origin", "fate", "next_id", "track_map")
 STATE_KEYS = ("st_ids", "st_count", "st_sums", "st_track", "st_age", "st_path")
 
@@ -148,6 +158,39 @@ def flows(p, direction):
     occ = p["occ"] or (None, None)
     f, g = direction in ("forward", "both"), direction in ("backward", "both")
     return (p["fw"] if f else None, p["bw"] if g else None, occ[0] if f else None, occ[1] if g else None)
+
+
+def device_case(case, cus=256):
+    """(B, H, W) of one of DEVICE_PATHS on a card of `cus` CUs."""
+    return (2 * cus if case[0] == sc.TWO_PER_CU else case[0],) + tuple(case[1:])
+
+
+def tiled(a, B):
+    """An array (or each array of a tuple or dict) over the distinct images, repeated to B images: image b is image b % K."""
+    if isinstance(a, dict):
+        return {k: tiled(v, B) for k, v in a.items()}
+    if isinstance(a, tuple):
+        return tuple(tiled(v, B) for v in a)
+    return None if a is None else np.ascontiguousarray(np.asarray(a)[np.arange(B) % len(a)])
+
+
+@functools.lru_cache(maxsize=None)
+def device_pair(family, B, H, W):
+    """(pair of the min(B, DISTINCT) distinct images, the same repeated to B images): the flood fill runs once per distinct image."""
+    small = pair(family, min(B, DISTINCT), H, W)
+    return small, (small if B <= DISTINCT else tiled(small, B))
+
+
+def run_pair_tiled(lib, small, full, obj0, obj1, rows, direction, M, device="cpu"):
+    """run_pair on a batch that repeats its distinct images, beside the reference's pushes of the distinct images alone (obj0, obj1:
+    their objects), repeated: -> run_pair's four.  The reference continues the code's own path of the distinct images."""
+    B, K = full["masks"][0].shape[0], small["masks"][0].shape[0]
+    H, W = obj0[0].shape[1:]
+    g1, g2 = run_pair(lib, full, tiled(obj0, B), tiled(obj1, B), rows, direction, M, device, ref=False)
+    r1 = tr.push(tr.empty_state(K, H, W, M), *obj0, np.zeros((K, 2, H, W), np.float32), None, None, None, rows, MIN_OVERLAP)
+    assert sc.bits(g1["st_path"]).tolist() == sc.bits(tiled(g1["st_path"][:K], B)).tolist(), "the repeats of an image differ"
+    r2 = tr.push(dict(r1[1], path=g1["st_path"][:K]), *obj1, *flows(small, direction), rows, MIN_OVERLAP)
+    return g1, g2, tiled(r1, B), tiled(r2, B)
 
 
 # ---- runners -------------------------------------------------------------------------------------------------------------------
