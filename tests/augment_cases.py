@@ -222,6 +222,47 @@ def hand_params(H, W, rects, r1, r2):
     return ag.AugmentParams(1).set_rects(0, rects).set_roll(0, r1, r2)
 
 
+# Shapes at which pf_aug_blocks caps a grid at 1024 workgroups, so that its threads go round their loops a second time
+# (tests/launch_paths.py: augment_grids): (B, H, W) = (1, 514, 2048), four pixels per thread in the main kernel, where rows 512 and
+# 513 are the second trip of the main kernel AND of the contrast pass; (2, 258, 1018), one pixel per thread, where the last 500
+# pixels are.  CAPPED_RECT holds 12 000 pixels: more than the 10 240 threads of the eraser's grid.
+CAPPED = ((1, 514, 2048), (2, 258, 1018))
+CAPPED_RECT = (10, 20, 120, 100)
+
+
+def capped_batch(shape):
+    """(img1, img2, flow, params, row0) of a CAPPED shape.  No hue step (RGB -> HSV is the one operation on which device and
+    emulation may differ): the chain is exact, so every byte is compared.  The frames are noise in [41, 160), mean L = 100.0, with
+    the rows from row0 = 512 on white at H = 514: the mean of L over the stacked pair is 100.60 with them and 99.61 when their sum
+    is left out, int(mean + 0.5) = 101 against 100 (contrast_means).  The contrast step comes second, behind a brightness step
+    of factor 1, in sample 0, third in the first set of sample 1 and first in its second set."""
+    from prior_flow_amd import augment as ag
+    B, H, W = shape
+    r = np.random.RandomState(17 + H)
+    i1, i2 = (r.randint(41, 160, (B, H, W, 3)).astype(np.uint8) for _ in range(2))
+    row0 = 512 if H > 512 else H
+    i1[:, row0:], i2[:, row0:] = 255, 255
+    fl = np.stack([make_flow(H, W, 60 + b) for b in range(B)])
+    p = ag.AugmentParams(B)
+    for second in (False, True):
+        p.set_colour(0, (0, 1, 2, 4), 1.0, 1.3, 0.8, shift=0, second=second)
+    p.set_rects(0, [CAPPED_RECT, (W - 40, H - 30, 99, 99)]).set_roll(0, -101)
+    if B > 1:
+        p.set_asymmetric_colour(1).set_colour(1, (2, 0, 1, 4), 1.2, 0.7, 1.1, shift=0)
+        p.set_colour(1, (1, 2, 4, 0), 0.9, 1.35, 1.25, shift=0, second=True)
+        p.set_rects(1, [CAPPED_RECT]).set_roll(1, 57, -60)          # the rolled rectangle straddles the seam
+    return i1, i2, fl, p.validate(H, W), row0
+
+
+def contrast_means(i1, i2, row0):
+    """int(mean(L) + 0.5) of the stacked pair (augment_ref.contrast_mean), and the same with the sum of the rows from row0 left
+    out of the numerator only: what a contrast pass that drops its second trip would hand to the main kernel."""
+    import augment_ref as ar
+    n = 2 * i1.shape[0] * i1.shape[1]
+    s = sum(int(ar.luma(i[:row0]).astype(np.int64).sum()) for i in (i1, i2))
+    return ar.contrast_mean([i1, i2]), (2 * s + n) // (2 * n)
+
+
 def small_odd_batch():
     """Three samples of 5 x 7 (H * W = 35, no multiple of 4): symmetric colour with the contrast step third, asymmetric colour with
     contrast second and last, and contrast first; a clipped rectangle each, symmetric and asymmetric rolls.  With 35 pixels

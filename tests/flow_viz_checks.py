@@ -24,6 +24,13 @@ MEAN_ERR_RTOL = 1e-5
 
 OS_KINDS = ("random", "tied", "equal", "zero", "inf", "nan")
 
+# Shapes at which pf_os_blocks caps the grid at 2048 workgroups, so that some thread goes round its loop once more than at any
+# smaller size (tests/launch_paths.py: os_grid, render_grids): a selection pass of 8 items per thread beyond 4 194 304 values, the
+# one-pixel length and colour kernels beyond 524 288 pixels (W % 4 != 0), the four-pixel ones beyond 524 288 quads.
+OS_CAPPED_N = 4200000
+OS_CAPPED_KINDS = ("random", "tied")
+RENDER_CAPPED = ((258, 2034), (1026, 2048))
+
 
 def golden():
     """The arrays of both fixture files (the second holds the images and the reference's my_cycle_warp of them)."""

@@ -53,9 +53,19 @@ def run(lib, jobs, alpha, device="cpu", fill=None, fill_t=0.0, zmax=sr.ZMAX, vma
     return out.cpu().numpy(), hole.cpu().numpy(), raw, acc.cpu().numpy()
 
 
+DEVICE_PATHS = sr.device_paths()            # the cases for pf_splat_acc_kernel's window, beside the sweep (splat_ref.py)
+
+
 def case_inputs(kind, shape, t, alpha, C, njobs):
     B, H, W = shape
-    return sr.inputs(kind, B, H, W, C, njobs, t, with_metric=alpha > 0)
+    make = sr.inputs if kind in sr.FAMILIES else sr.device_inputs
+    return make(kind, B, H, W, C, njobs, t, with_metric=alpha > 0)
+
+
+def reached(case):
+    """The window's paths (tests/launch_paths.py) that the jobs of a case reach."""
+    import launch_paths as lp
+    return lp.splat_case_paths(case_inputs(*case), *case[1][1:])
 
 
 def check_case(lib, kind, shape, t, alpha, C, njobs, device="cpu", refs=None):

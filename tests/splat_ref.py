@@ -109,6 +109,72 @@ def inputs(kind: str, B: int, H: int, W: int, C: int, njobs: int, t: float, with
     return jobs
 
 
+# ---- cases for the code that exists only in pf_splat.hip: the LDS window of pf_splat_acc_kernel ------------------------------------
+# The sweep above reaches the window's branches at (1, 64, 128) only and never an unplaced centre, a map narrower than the window,
+# a second image beside a second tile column, or a third column (tests/launch_paths.py: splat_window_paths says what a case
+# reaches; tests/test_launch_paths.py shows it for these and for the sweep).  Every flow value here is a multiple of 1/4, so with
+# tau in {1/4, 1/2, 1} and the 1/8 of a four-job case every landing, and with it the window-or-direct choice of every tap, is exact
+# in fp32.
+DEVICE_SHAPES = ((3, 20, 200), (2, 12, 72), (2, 9, 80), (2, 16, 65))     # four columns / W < window / W = window / one-pixel column
+DEVICE_FAMILIES = ("centre_bad", "torn_x", "torn_y", "margin", "back")
+DEVICE_SETTINGS = ((0.5, 0.0, 3, 2), (1.0, 0.5, 4, 4), (0.25, 0.0, 1, 1))          # (t, alpha, C, njobs); two jobs: the blend fill
+CENTRE_FAR = ("centre_far", (3, 20, 200), 0.5, 0.0, 3, 2)                 # held to the emulation's bits only (see device_paths)
+TILE_Y, TILE_X = 8, 64                                                    # pf_splat.hip kTileY, kTileX
+
+
+def tile_centres(H: int, W: int):
+    """(cy, cx) of every tile of pf_splat_acc_kernel, row-major: min(ty0 + 4, H - 1), min(tx0 + 32, W - 1)."""
+    return [(min(ty + TILE_Y // 2, H - 1), min(tx + TILE_X // 2, W - 1)) for ty in range(0, H, TILE_Y) for tx in range(0, W, TILE_X)]
+
+
+def device_flow(kind: str, H: int, W: int, b: int, j: int, tau: float):
+    """Flow [2,H,W] float32 of image b, job j: a family in tile-relative coordinates, plus an integer shift per image (3 b, -b) and
+    a quarter-step shift per job (j / 4, j / 4)."""
+    y, x = np.mgrid[0:H, 0:W]
+    ry, rx = y % TILE_Y, x % TILE_X
+    zero = np.zeros((H, W))
+    if kind in ("centre_bad", "centre_far"):
+        u, v = zero + 5.25, zero - 1.75
+    elif kind == "torn_x":
+        u, v = np.where(rx < TILE_X // 2, 3.25, 40.5), zero + 0.75
+    elif kind == "torn_y":
+        u, v = zero + 2.5, np.where(ry < TILE_Y // 2, 1.25, 9.5)
+    elif kind == "margin":
+        u = np.where(rx < 8, -8.5, np.where(rx >= TILE_X - 8, 8.5, 0.0))
+        v = np.where(ry < 2, -4.5, np.where(ry >= TILE_Y - 2, 4.5, 0.0))
+    elif kind == "back":
+        u, v = zero - 2.25 * W - 0.5, zero + 0.5
+    else:
+        raise ValueError(kind)
+    f = np.stack([u + 3 * b + 0.25 * j, v - b + 0.25 * j]).astype(np.float32)
+    assert np.array_equal(f * 4, np.rint(f * 4))
+    if kind == "centre_bad":        # the tile centres carry NaN, +inf, a landing beyond 2^30 and -inf in turn
+        bad = ((0, np.nan), (1, np.inf), (0, 3.0e9 / max(abs(tau), 0.25)), (1, -np.inf))
+        for k, (cy, cx) in enumerate(tile_centres(H, W)):
+            c, value = bad[(k + b + j) % 4]
+            f[c, cy, cx] = value
+    elif kind == "centre_far":      # finite and inside [2^28, 2^30) at tau >= 1/2: the pixel is splatted, its tile's window is not placed
+        for cy, cx in tile_centres(H, W):
+            f[0, cy, cx] = 6.0e8
+    return f
+
+
+def device_inputs(kind: str, B: int, H: int, W: int, C: int, njobs: int, t: float, with_metric: bool):
+    """The jobs of a DEVICE_PATHS case: frames, metrics and masks as `inputs` makes them, the flows of device_flow."""
+    jobs = inputs("integer", B, H, W, C, njobs, t, with_metric, dirty=False)
+    for j, q in enumerate(jobs):
+        for b in range(B):
+            q["flow"][b] = device_flow(kind, H, W, b, j, q["tau"])
+    return jobs
+
+
+def device_paths():
+    """(kind, shape, t, alpha, C, njobs) of every case for the window.  `centre_far` is not among them: a centre that lands in
+    [2^28, 2^30) is a pixel with |tau u| = 3e8, which takes dq = 2 eps (W + max |tau u|) to 72 pixels and leaves the float64
+    restatement undecided on every pixel; that case (CENTRE_FAR) is held to the emulation's bits alone."""
+    return [(k, s) + st for k in DEVICE_FAMILIES for s in DEVICE_SHAPES for st in DEVICE_SETTINGS]
+
+
 def fill_blend(f0, f1, t):
     """(1 - t) f0 + t f1 as the kernel evaluates it: every step a rounded fp32 operation."""
     t = np.float32(t)

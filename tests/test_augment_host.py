@@ -157,6 +157,34 @@ def test_odd_shape_against_the_restatement(emu):
         assert ac.same_flow(got[2][b], want[2]) and np.array_equal(got[3][b], want[3]), b
 
 
+@pytest.mark.parametrize("shape", ac.CAPPED, ids=lambda s: "x".join(map(str, s)))
+def test_capped_shapes_against_the_restatement(emu, shape):
+    """The host twin of the device's capped-grid cases (tests/test_hip_augment.py): the emulation equals the restatement on every
+    byte (no hue step in these chains), and at H = 514 the content is such that the rows of the contrast pass's second trip move
+    int(mean + 0.5): the restatement's images with the mean of the shortened sum differ from the right ones."""
+    B, H, W = shape
+    i1, i2, fl, p, row0 = ac.capped_batch(shape)
+    got = ac.run(emu, i1, i2, fl, p)
+    for b in range(B):
+        row = p.row(b)
+        with np.errstate(invalid="ignore"):
+            want = ar.augment_sample(i1[b], i2[b], fl[b], row)
+        assert ac.image_diff(np.stack([got[0][b], got[1][b]]), np.stack(want[:2])) == (0.0, 0.0), b
+        assert ac.same_flow(got[2][b], want[2]) and np.array_equal(got[3][b], want[3]), b
+        assert ac.CAPPED_RECT in row["rects"] and "seam" in ac.features(row, H, W)
+    if row0 < H:
+        full, short = ac.contrast_means(i1[0], i2[0], row0)
+        print(f"{H}x{W}: int(mean + 0.5) of the stacked pair {full}, without the sum of rows {row0}..{H - 1}: {short}")
+        assert (full, short) == (101, 100)
+        s = p.row(0)["set_a"]
+        assert not p.row(0)["asym_colour"] and s["order"][:2] == [0, 1] and s["fb"] == 1.0 and s["fc"] != 1.0
+        right, wrong = (ar.contrast(i1[0], s["fc"], m) for m in (full, short))
+        assert np.array_equal(right, ar.jitter([i1[0], i2[0]], [0, 1, 4, 4], s["fb"], s["fc"], s["fs"], 0)[0])
+        share = float((right[:row0] != wrong[:row0]).mean())
+        print(f"bytes of rows 0..{row0 - 1} after the contrast step that the shortened sum changes: {share:.1%}")
+        assert share > 0.1
+
+
 def test_untrusted_rows_stay_inside_the_maps(emu, gold):
     """Rolls of many widths, rectangles that start outside or have no area, unknown operations: reduced, dropped, skipped."""
     H, W = ac.SIZES[0]

@@ -376,7 +376,8 @@ def test_odd_shape_takes_the_tail_of_the_contrast_pass(lib):
 
 
 def test_large_shape_against_the_restatement(lib):
-    """512 x 1024, B = 2, the only large shape: more than one workgroup per plane, grid-stride loops; under bar 2."""
+    """512 x 1024, B = 2: 512 workgroups per plane, below the cap of 1024, so every thread goes round its loop once (the shapes
+    at which the loops make a second trip: test_capped_grids_against_the_restatement_and_the_emulation); under bar 2."""
     from prior_flow_amd import augment as ag
     H, W, B = 512, 1024, 2
     r = np.random.RandomState(9)
@@ -394,3 +395,31 @@ def test_large_shape_against_the_restatement(lib):
         print(f"512x1024 sample {b}: share of differing bytes {share:.2e}, worst {worst:.0f}")
         assert share <= ac.CAP_SHARE and worst <= ac.CAP_CHAIN
         assert ac.same_flow(got[2][b], wf) and np.array_equal(got[3][b], wv)
+
+
+@pytest.mark.parametrize("shape", ac.CAPPED, ids=lambda s: "x".join(map(str, s)))
+def test_capped_grids_against_the_restatement_and_the_emulation(lib, emu, shape):
+    """The shapes at which pf_aug_blocks caps a grid at 1024 workgroups and its threads make a second trip: (1, 514, 2048), four
+    pixels per thread, rows 512 and 513 in the second trip of the main kernel and of the contrast pass, whose sum over those
+    rows moves int(mean + 0.5) from 100 to 101 (tests/test_augment_host.py shows it); (2, 258, 1018), one pixel per thread, the
+    last 500 pixels; and a rectangle of 12 000 pixels for the 10 240 threads of the eraser.  Under bar 2 against the
+    restatement, and equal to the emulation on every byte (no hue step in these chains)."""
+    import launch_paths as lp
+    B, H, W = shape
+    grids = dict(lp.augment_grids(H, W), erase=lp.aug_erase_grid(ac.CAPPED_RECT, H, W))
+    print(f"{B}x{H}x{W}: " + ", ".join(f"{k} {g[1]} of {g[0]} wanted, {g[2]} trip(s)" for k, g in grids.items()))
+    assert grids["erase"][2] == 2 and [g[2] for k, g in grids.items() if k.startswith("main")] == [2]
+    assert grids["contrast"][2] == (2 if H == 514 else 1)
+    assert emu is not None
+    i1, i2, fl, p, row0 = ac.capped_batch(shape)
+    got = ac.run(lib, i1, i2, fl, p, DEV)
+    host = ac.run(emu, i1, i2, fl, p)
+    for b in range(B):
+        with np.errstate(invalid="ignore"):
+            w1, w2, wf, wv = ar.augment_sample(i1[b], i2[b], fl[b], p.row(b))
+        share, worst = ac.image_diff(np.stack([got[0][b], got[1][b]]), np.stack([w1, w2]))
+        print(f"{H}x{W} sample {b}: share of differing bytes {share:.2e}, worst {worst:.0f}")
+        assert share <= ac.CAP_SHARE and worst <= ac.CAP_CHAIN
+        assert ac.same_flow(got[2][b], wf) and np.array_equal(got[3][b], wv)
+    assert all(np.array_equal(g, h, equal_nan=True) for g, h in zip(got, host))
+    assert not np.isnan(got[0]).any() and not np.isnan(got[1]).any() and not np.isnan(got[3]).any()

@@ -62,6 +62,29 @@ def test_order_stat_odd_sizes(lib, n):
         assert got.view(np.uint32).tolist() == ck.os_expected(x, k).view(np.uint32).tolist()
 
 
+@pytest.mark.parametrize("kind", ck.OS_CAPPED_KINDS)
+def test_order_stat_beyond_the_grid_cap(lib, kind):
+    """n = 4 200 000 > 2048 workgroups x 256 threads x 8 items: pf_os_blocks caps the grid of the three selection passes and
+    some threads go round their loop a ninth time (no smaller case reaches the cap: tests/test_launch_paths.py).  B = 2, the
+    ranks of ck.os_ranks, bit for bit against np.sort."""
+    import launch_paths as lp
+    n, B = ck.OS_CAPPED_N, 2
+    want, launched, trips = lp.os_grid(n, lp.OS_SELECT_PER)
+    print(f"[flow_viz] order statistic n = {n}: {launched} of {want} workgroups wanted per image, {trips} trips")
+    assert launched < want and trips == lp.OS_SELECT_PER + 1
+    x = ck.os_input(kind, B, n, seed=61)
+    first_trips = lp.OS_MAX_BLOCKS * lp.ELEM_BLOCK * lp.OS_SELECT_PER
+    if kind == "tied":                                  # the two largest ranks are values that only the ninth trip reads
+        x[:, first_trips:] = np.float32(1.0)
+    s = np.sort(x, axis=1)
+    assert not np.isnan(s).any() and (kind != "tied" or (len(np.unique(s)) <= 17 and s[0, -1] == 1.0 and (x[:, :first_trips] < 1).all()))
+    # without the ninth trip's values the rank 0.95 n falls on another value
+    assert (np.sort(x[:, :first_trips], axis=1)[:, int(0.95 * n)] != s[:, int(0.95 * n)]).all() or kind == "tied"
+    for k in ck.os_ranks(n):
+        got = ck.run_order_stat(lib, x, k, device=DEV)
+        assert got.view(np.uint32).tolist() == s[:, k].view(np.uint32).tolist(), (kind, k, got, s[:, k])
+
+
 def test_order_stat_nan_rules(lib):
     x = np.array([[3.0, np.nan, 1.0, np.nan, 2.0], [np.nan] * 5, [0.5, np.inf, np.nan, 0.25, 0.0]], np.float32)
     assert ck.run_order_stat(lib, x, 2, device=DEV).tolist() == [3.0, 0.0, 0.5]
@@ -108,6 +131,31 @@ def test_render_512x1024_matches_float64(lib, mode):
         ck.colour_figures(img, fr.render(flow, mode, bgr=bgr), f"device {mode} {layout} bgr={bgr} 512x1024 B=2 against float64")
     if mode == "omni":
         assert np.abs(length - fr.veclen_spherical(flow)).max() <= ck.SD_ATOL
+
+
+@pytest.mark.parametrize("mode,layout", [("omni", "hwc"), ("plane", "chw")])
+@pytest.mark.parametrize("H,W", ck.RENDER_CAPPED)
+def test_render_beyond_the_grid_cap_matches_float64(lib, mode, layout, H, W):
+    """258 x 2034 (W % 4 != 0: one pixel per thread, 524 772 pixels) and 1026 x 2048 (four pixels per thread, 525 312 quads): the
+    grids of the length pass and of the colour kernel are capped at 2048 workgroups and their first threads make a second trip,
+    which holds the last 484 pixels and the last two rows.  Under the colour bar against float64; the length map to SD_ATOL."""
+    import launch_paths as lp
+    (form, (want, launched, trips)), = lp.render_grids(H, W).items()
+    print(f"[flow_viz] render {H}x{W}, {form}: {launched} of {want} workgroups wanted, {trips} trips")
+    assert launched < want and trips == 2
+    flow = fc.make_flow(1, H, W, seed=27)
+    img, length, clip = ck.run_render(lib, flow, mode, layout=layout, device=DEV)
+    img = img if layout == "hwc" else img.transpose(0, 2, 3, 1)
+    ck.colour_figures(img, fr.render(flow, mode), f"device {mode} {layout} {H}x{W} against float64")
+    want_len = fr.lengths(flow, mode)
+    d = np.abs(length - want_len).max()
+    print(f"[flow_viz] device len {mode} {H}x{W} against float64: {d:.3e}")
+    # omni: the bar of the great-circle length; plane: sqrtf(u u + v v), four roundings of half an ulp at most
+    assert d <= (ck.SD_ATOL if mode == "omni" else 2.0 ** -22 * want_len.max())
+    k = int(0.95 * H * W) if mode == "omni" else H * W - 1          # the clip is the device's own length map's order statistic
+    assert clip.view(np.uint32).tolist() == np.sort(length[0], axis=None)[k:k + 1].view(np.uint32).tolist()
+    tail = slice(lp.OS_MAX_BLOCKS * lp.ELEM_BLOCK * (4 if form == "four_pixel" else 1), None)      # the second trip's pixels
+    assert len(np.unique(img.reshape(-1, 3)[tail], axis=0)) > 10
 
 
 @pytest.mark.parametrize("mode", ["omni", "plane"])

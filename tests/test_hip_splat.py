@@ -56,6 +56,50 @@ def test_device_matches_float64_and_the_emulation(lib, emu, kind):
     print(f"{kind}: {n} cases, worst err / bound {worst:.4f}; alpha > 0: {differ} of {values} values differ from the emulation")
 
 
+@pytest.mark.parametrize("kind", sr.DEVICE_FAMILIES)
+def test_window_cases_match_float64_and_the_emulation(lib, emu, kind):
+    """sc.DEVICE_PATHS: the code of pf_splat_acc_kernel that no other file holds -- where a window is placed (and that it is placed
+    at the tile when the centre pixel lands nowhere), its columns modulo a width below, at and above its own, the
+    window-or-direct choice of a tap, the flush -- at four tile columns, at 64 < W <= 80 and with blockIdx.z > 0 beside tx0 > 0.
+    Every case holds the float64 bounds; at alpha = 0 out, the hole byte and the raw sums are the emulation's bits (the
+    emulation adds every tap directly: where an add is made must not change a bit); a second run and the jobs reversed give the
+    first run's bits; the sums are all-zero afterwards.  `centre_far` (a centre that is splatted but lands beyond 2^28) is
+    beyond the reference and is held to the emulation's bits.  Prints the paths each case reaches (tests/launch_paths.py)."""
+    cases = [c for c in sc.DEVICE_PATHS if c[0] == kind] + ([sr.CENTRE_FAR] if kind == "centre_bad" else [])
+    worst, differ, values, union = 0.0, 0, 0, set()
+    for case in cases:
+        _, (B, H, W), t, alpha, C, njobs = case
+        paths = sc.reached(case)
+        union |= paths
+        print(f"{case}: reaches {sorted(paths)}")
+        if case[0] == "centre_far":
+            jobs = sc.case_inputs(*case)
+            out, hole, raw, after = sc.run(lib, jobs, alpha, "cuda")
+            h = sc.run(emu, jobs, alpha)
+            assert not after.any()
+        else:
+            refs = {}
+            out, hole, raw, figs = sc.check_case(lib, *case, device="cuda", refs=refs)
+            h = sc.check_case(emu, *case, refs=refs)
+            worst = max([worst] + [f["err_over_tol"] for f in figs])
+        if alpha == 0.0:
+            assert same((out, hole, raw), h[:3]), case
+        else:
+            differ += int((bits(out) != bits(h[0])).sum()) + int((raw != h[2]).sum())
+            values += out.size + raw.size
+        jobs = sc.case_inputs(*case)
+        fill = (jobs[0]["src"], jobs[1]["src"]) if njobs == 2 and case[0] != "centre_far" else None
+        again = sc.run(lib, jobs, alpha, "cuda", fill, t if fill else 0.0)
+        back = sc.run(lib, jobs[::-1], alpha, "cuda", fill, t if fill else 0.0)
+        assert same((out, hole, raw), again[:3]) and not again[3].any(), case
+        assert same((out, hole, raw), back[:3]) and not back[3].any(), case          # the same fill maps in the same order
+    print(f"{kind}: {len(cases)} cases, worst err / bound {worst:.4f}; alpha > 0: {differ} of {values} values differ from the "
+          f"emulation; reached in all: {sorted(union)}")
+    assert {"batched_columns", "three_columns", "narrow_map", "width_is_window", "clipped_centre"} <= union
+    assert {"centre_bad": {"centre_unplaced"}, "torn_x": {"direct_x", "split_pixel"}, "torn_y": {"direct_y", "split_pixel"},
+            "margin": {"direct_x", "direct_y", "split_pixel"}, "back": {"negative_origin"}}[kind] <= union
+
+
 def test_same_bits_on_every_run_and_under_every_job_order(lib):
     """The same call twice and the call with its jobs reversed: out, the hole byte and the raw sums are the same bits, `collapse`
     at 64x128 (every pixel of four jobs onto one target) included."""

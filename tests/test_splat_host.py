@@ -117,6 +117,33 @@ def test_emulation_matches_float64_over_the_sweep(emu, kind):
     assert n == (36 if kind == "expand" else 54) * 3
 
 
+@pytest.mark.parametrize("kind", sr.DEVICE_FAMILIES)
+def test_emulation_matches_float64_on_the_window_cases(emu, kind):
+    """The host twin of the device's window cases (sc.DEVICE_PATHS; tests/test_hip_splat.py): the emulation has no window, so
+    this says that the reference and its bounds hold on these flows before the device is held to them.  `centre_far` is shown to
+    be beyond the reference: every pixel undecided, which is why the device is held to the emulation's bits there."""
+    worst = und = 0.0
+    n = 0
+    for case in sc.DEVICE_PATHS:
+        if case[0] != kind:
+            continue
+        out, hole, raw, figs = sc.check_case(emu, *case)
+        worst = max([worst] + [f["err_over_tol"] for f in figs])
+        und = max([und] + [f["undecided"] for f in figs])
+        assert raw.any() and not hole.all()
+        n += 1
+    print(f"{kind}: {n} cases, worst err / bound {worst:.4f}, most undecided {und:.4%}")
+    assert n == len(sr.DEVICE_SHAPES) * len(sr.DEVICE_SETTINGS)
+    if kind == "centre_bad":
+        _, B, H, W = (sr.CENTRE_FAR[0],) + sr.CENTRE_FAR[1]
+        jobs = sc.case_inputs(*sr.CENTRE_FAR)
+        ref = sr.reference(jobs, 0, 0.0)
+        print(f"centre_far: {1 - ref['decided'].mean():.1%} of the pixels undecided")
+        assert not ref["decided"].any()
+        out, hole, raw, after = sc.run(emu, jobs, 0.0)
+        assert raw.any() and not after.any() and np.isfinite(out).all()
+
+
 # ---- seeded faults ---------------------------------------------------------------------------------------------------------------
 # fault -> the case it is seeded at: (kind, shape, t, alpha, C, njobs)
 FAULT_AT = {
